@@ -39,6 +39,18 @@ at every N.
 `bench.py --gpus N` with N > 1 and no launcher around it starts its N ranks itself
 (torch.distributed.run in a child process, self_launch); under a launcher WORLD_SIZE must equal N.
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) does what the headline figure needs and no
+more: it builds the workload, warms up, times the K steps and prints the line (its "verified",
+"cpu_baseline", roofline.traffic / issue / gather are null and "also" is empty; the histogram's
+total is still checked against the packet count).  Everything else described above -- the oracle
+check of the last timed launch, the CPU baseline, the rocprofv3 --pmc child passes and the --also
+configs -- runs under --full, where --no-verify, --no-cpu-baseline, --no-pmc and --also narrow it.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed launch of the --config
+workload returned on rank 0 (dump_outputs): the verdict histogram and a fixed, seeded sample of the
+per-packet 64-bit results, as float64 .npy files.  The packets are seeded, so two builds run with
+the same arguments can be compared file for file.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -89,6 +101,14 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="c4", choices=sorted(workloads.CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: verify the last launch against the oracle, measure "
+                         "the CPU baseline, the rocprofv3 --pmc rooflines and the --also configs "
+                         "(off by default: a plain run only times --config)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write the last timed launch's outputs (rank 0's shard "
+                         "of --config) as DIR/<name>.npy, float64: hist, and a fixed seeded sample of "
+                         "the per-packet results as ret_index / ret_lo32 / ret_hi32")
     ap.add_argument("--packets", type=int, default=0,
                     help="packets of the whole batch (strong) or per GPU (weak); default per config")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
@@ -118,7 +138,13 @@ def parse(argv=None):
     ap.add_argument("--also-max-steps", type=int, default=4000)
     ap.add_argument("--launch", default="eager", choices=["graph", "eager"],
                     help="eager: direct launches (default); graph: each step replays a captured HIP graph (measured 1.6%% slower on C2-C4, profiles/r01/graph_ab)")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not a.full:   # a plain run: the timed steps of --config and nothing else
+        a.no_cpu_baseline = a.no_pmc = a.no_verify = True
+        a.also = ""
+    return a
 
 
 DEFAULT_PACKETS = {"nop200": 1 << 24, "alu200": 1 << 24, "c0": 1 << 26, "c2": 1 << 20, "c3": 1 << 24,
@@ -371,8 +397,7 @@ def pmc_traffic(a, w, total, layout, cfg=None):
     cfg = cfg or a.config
     out = a.pmc_dir or tempfile.mkdtemp(prefix="ebpf_pmc_")
     child = [sys.executable, os.path.abspath(__file__), "--config", cfg, "--packets",
-             str(total), "--steps", "2", "--warmup", "1", "--variant", str(a.variant),
-             "--no-cpu-baseline", "--no-pmc", "--no-verify", "--also="]
+             str(total), "--steps", "2", "--warmup", "1", "--variant", str(a.variant)]  # a plain run
     vals = {}
     # general kernels (divergent programs): also the instruction counts of the issue roofline
     passes = [("FETCH_SIZE",), ("WRITE_SIZE",)]
@@ -458,6 +483,27 @@ def gather_roofline(insts, kern_ms, groups):
             "model": "TCP_TOTAL_CACHE_ACCESSES / (%.3f per CU cycle x %d CUs x %.1f GHz): "
                      "tools/ubench/gather.hip mode i, this run's PMC pass" % (
                          GATHER_ACCESSES_PER_CU_CYCLE, CUS, CLOCK_GHZ)}
+
+
+DUMP_SAMPLE = 1 << 20  # per-packet results written by --dump-outputs (3 float64 arrays: 24 MiB)
+
+
+def dump_outputs(outdir, torch, d_ret, n, d_hist):
+    """--dump-outputs: what a caller of the timed launch receives, from its last timed step, as
+    float64 .npy files (every value exact): hist.npy, the 257-bin verdict histogram (summed over
+    the ranks when N > 1), and DUMP_SAMPLE of this rank's n per-packet results (all of them when
+    n is smaller) at fixed, seeded positions: ret_index.npy (position in the shard, ascending),
+    ret_lo32.npy and ret_hi32.npy (the low and high halves of the 64-bit result)."""
+    os.makedirs(outdir, exist_ok=True)
+    if n <= DUMP_SAMPLE:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(20240607).integers(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+    ret = d_ret[: max(n, 1)][torch.from_numpy(idx).to(d_ret.device)].cpu().numpy().view(np.uint64)
+    np.save(os.path.join(outdir, "hist.npy"), d_hist.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(outdir, "ret_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(outdir, "ret_lo32.npy"), (ret & np.uint64(0xffffffff)).astype(np.float64))
+    np.save(os.path.join(outdir, "ret_hi32.npy"), (ret >> np.uint64(32)).astype(np.float64))
 
 
 def measure(a, cfg, packets, torch, dist, world, rank, local, dev, also=False):
@@ -583,6 +629,8 @@ def measure(a, cfg, packets, torch, dist, world, rank, local, dev, also=False):
     achieved = bytes_per_launch / (kern_ms * 1e-3) / 1e9
     exec_name, layout, translate_ms, build_ms = prog.exec_info(local)
 
+    if a.dump_outputs and not also and rank == 0:
+        dump_outputs(a.dump_outputs, torch, d_ret, n, d_hist)
     hist = d_hist.cpu().numpy()
     faulted = int(hist[256])
     vinfo = {"verified": None}

@@ -254,3 +254,54 @@ def test_bench_issue_roofline():
     assert r["bound"] == "valu-issue" and abs(r["floor_ms"] - 1.0) < 1e-9
     assert r["frac"] == 0.5 and r["salu_per_group"] == 10.0 and r["vmem_rd_per_group"] == 1.0
     assert b.issue_roofline({}, 1.0, 1) is None
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(
+        "bench_mod", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    return b
+
+
+def test_bench_plain_and_full_arguments():
+    """A plain bench.py run times --config and nothing else; --full turns on the oracle check, the
+    CPU baseline, the PMC passes and the --also configs, which its own switches still narrow."""
+    b = _bench_module()
+    a = b.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full) == (7, 2, False)
+    assert a.no_verify and a.no_cpu_baseline and a.no_pmc and a.also == "" and a.dump_outputs == ""
+    a = b.parse(["--also", "c5", "--dump-outputs", "d"])   # without --full nothing else is measured
+    assert a.also == "" and a.no_verify and a.dump_outputs == "d"
+    a = b.parse(["--full"])
+    assert not (a.no_verify or a.no_cpu_baseline or a.no_pmc)
+    assert a.also.split(",") == ["c2", "c3", "c5", "c4h", "c4c", "c3l"]
+    a = b.parse(["--full", "--no-pmc", "--also", "c5"])
+    assert a.no_pmc and not a.no_verify and a.also == "c5"
+    with pytest.raises(SystemExit):
+        b.parse(["--steps", "0"])
+
+
+@pytest.mark.parametrize("n", [1000, (1 << 20) + 12345])
+def test_bench_dump_outputs(tmp_path, n):
+    """--dump-outputs: float64 files that hold the histogram and the (sampled) 64-bit results
+    exactly, at the same positions from run to run, within 64 MB."""
+    import numpy as np
+    import torch
+    b = _bench_module()
+    ret =(np.arange(n, dtype=np.uint64) * np.uint64(0x9e3779b97f4a7c15)) ^ np.uint64(1 << 63)
+    d_ret = torch.from_numpy(ret.view(np.int64))
+    hist = torch.arange(257, dtype=torch.int64) * (1 << 40)
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), torch, d_ret, n, hist)
+    got = {f: np.load(tmp_path / "a" / (f + ".npy")) for f in ("hist", "ret_index", "ret_lo32", "ret_hi32")}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
+    for f, v in got.items():
+        np.testing.assert_array_equal(v, np.load(tmp_path / "b" / (f + ".npy")))
+    np.testing.assert_array_equal(got["hist"], hist.numpy().astype(np.float64))
+    idx = got["ret_index"].astype(np.int64)
+    assert len(idx) == min(n, b.DUMP_SAMPLE) and (np.diff(idx) >= 0).all() and 0 <= idx[0] and idx[-1] < n
+    back = (got["ret_hi32"].astype(np.uint64) << np.uint64(32)) | got["ret_lo32"].astype(np.uint64)
+    np.testing.assert_array_equal(back, ret[idx])

@@ -254,7 +254,7 @@ def test_bench_two_ranks_gloo(launcher):
     import json
     total = (1 << 21) + 77
     args = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
-            "--packets", str(total), "--no-cpu-baseline", "--no-pmc", "--also", "c5"]
+            "--packets", str(total), "--full", "--no-cpu-baseline", "--no-pmc", "--also", "c5"]
     if launcher == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                "--master-addr", "127.0.0.1", "--master-port", "29631"] + args

@@ -21,7 +21,7 @@ for k in $(seq 0 $((ROUNDS - 1))); do
         *) envs+=("$p") ;;
       esac
     done
-    cmd=(timeout -k 10 200 python bench.py --also= --no-pmc --no-cpu-baseline --steps "$STEPS"
+    cmd=(timeout -k 10 200 python bench.py --full --also= --no-pmc --no-cpu-baseline --steps "$STEPS"
          --warmup 5 --config "$cfg" "${args[@]}")
     if [ -n "${DRY:-}" ]; then echo "${envs[*]} ${cmd[*]} > $O/${name}_$k.json"; continue; fi
     ( for e in "${envs[@]}"; do export "$e"; done

@@ -13,7 +13,7 @@ if [ -n "${TESTS:-}" ]; then
 fi
 for c in ${BENCH:-}; do
   echo "== bench $c $(date +%T)"
-  timeout -k 10 300 python -u bench.py --config $c --also= --no-pmc --no-cpu-baseline --steps ${STEPS:-20} --warmup 5 ${BENCH_ARGS:-} > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err"
+  timeout -k 10 300 python -u bench.py --full --config $c --also= --no-pmc --no-cpu-baseline --steps ${STEPS:-20} --warmup 5 ${BENCH_ARGS:-} > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err"
   rc=$?; cat "$OUT/bench_$c.json"; tail -3 "$OUT/bench_$c.err"; [ $rc -eq 0 ] || exit $rc
 done
 echo "== done $(date +%T)"

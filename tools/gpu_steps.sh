@@ -25,7 +25,7 @@ for st in "$@"; do
       tail -1 "$O/smoke.log" ;;
     bench:*)
       rest="${st#bench:}"; name="${rest%%:*}"; args="${rest#*:}"
-      timeout -k 10 400 python3 bench.py --pmc-dir "$O/pmc_$name" $args > "$O/bench_$name.json" \
+      timeout -k 10 400 python3 bench.py --full --pmc-dir "$O/pmc_$name" $args > "$O/bench_$name.json" \
         2> "$O/bench_$name.err" || { tail -5 "$O/bench_$name.err"; cat "$O/bench_$name.json"; exit 1; }
       cat "$O/bench_$name.json" ;;
     prof:*)

@@ -9,7 +9,7 @@ mkdir -p "$O"
 run() {
   local n=$1; shift
   for r in 1 2 3; do
-    env "$@" timeout -k 10 120 python3 bench.py --config c3l --also= --no-pmc --no-cpu-baseline --steps 200 --warmup 20 > "$O/$n.$r.json" 2>/dev/null || return 1
+    env "$@" timeout -k 10 120 python3 bench.py --full --config c3l --also= --no-pmc --no-cpu-baseline --steps 200 --warmup 20 > "$O/$n.$r.json" 2>/dev/null || return 1
     python3 -c "import json; d=json.load(open('$O/$n.$r.json')); print('$n', d['roofline']['kernel_ms'], d['roofline']['frac'], d['verified'])"
   done
 }
