@@ -14,6 +14,7 @@
 
 #include "../dprog.h"
 #include "../jhash.h"
+#include "host/runtime.h"
 
 namespace {
 

@@ -21,7 +21,7 @@
 
 #include "asm_cc.h"
 #include "asm_handlers.h"
-#include "internal.h"
+#include "runtime.h"
 
 int asm_lower(const dprog_host &xl, int mode, const std::vector<dp_map> &table,
 	      std::vector<dp_entry> &out, uint32_t *stack_stride, std::string *err);

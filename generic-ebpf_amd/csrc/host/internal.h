@@ -52,7 +52,7 @@ struct map_mirror {
 	// host staging copy of the last upload (hashtable: the device table); a new upload makes a
 	// new one, so a batch that captured it keeps the table its packets read
 	std::shared_ptr<const std::vector<uint8_t>> image;
-	// Cross-stream order of the mirror's users on its device (gpu_runtime.cpp mirror_read /
+	// Cross-stream order of the mirror's users on its device (map_mirror.cpp mirror_read /
 	// mirror_write_*): a write (an upload, or a batch's map writes landing) waits for every
 	// launch that read the mirror on another stream since the previous write, and a launch on a
 	// stream waits for the last write made on another stream.
@@ -207,6 +207,7 @@ struct dprog_host {
 	bool asm_pktv = false;               // packet loads at run-time offsets (LDXPKTV), no packet stores
 	bool asm_hdrlds = false;             // ... and keep them in LDS for run-time-offset loads
 	                                     // (asm_program_hdrlds)
+	bool asm_keep = false;               // asm_pktv: staged launches run in keep mode (DP_VF_KEEP)
 	uint32_t max_stack = 0;
 	double translate_ms = 0;             // host time of translate_program
 	// Map writes of a device batch (ebpf_gpu.h): the write log holds max_updates records per
@@ -257,19 +258,21 @@ void obj_init(struct ebpf_env *ee, struct ebpf_obj *eo);
 // translate.cpp
 int translate_program(struct ebpf_prog *ep, dprog_host &out);
 
-// gpu_runtime.cpp
+// gpu_runtime.cpp (the GPU backend's own interfaces: runtime.h)
 void set_last_error(const std::string &msg);
 // Translate the program (once; thread-safe).  0, or the translation's error.
 int prog_ensure_translated(struct ebpf_prog *ep);
 // the calling thread's device for the host-buffer entry points (ebpf_gpu_set_device)
 int current_device();
+// map_mirror.cpp
 // Copy a device batch's map writes back into the host copy (no-op unless em->dev_dirty).
 // Returns 0, or EIO when the copy failed (the map then stays marked dirty).
 int map_pull_device_writes(struct ebpf_map *em);
 // A batch on `device` wrote the map (its writes land on `stream`, a hipStream_t).
 void map_mark_device_write(struct ebpf_map *em, int device, void *stream);
-void prog_release_device_state(struct ebpf_prog *ep);
 void map_release_device_state(struct ebpf_map *em);
+// gpu_runtime.cpp
+void prog_release_device_state(struct ebpf_prog *ep);
 
 // The calling thread's current HIP device, restored when the scope ends: a C library must not
 // change it (every exported entry point that selects a device holds one).

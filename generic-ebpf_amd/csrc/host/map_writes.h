@@ -6,7 +6,7 @@
 // One map of a map-writing program, as the apply kernels see it (dprog_host upd_maps /
 // hupd_maps / atomic_maps).  Only UPD_DEVICE maps' records land here; the records of UPD_HOST
 // maps (hashtables, arrays mixing counter updates and stores) are replayed on the host after the
-// batch (gpu_runtime.cpp upd_apply_host), and UPD_ATOMIC maps log nothing (their counter updates
+// batch (map_write_log.cpp upd_apply_host), and UPD_ATOMIC maps log nothing (their counter updates
 // went into the delta area during the batch).
 enum { UPD_NONE = 0, UPD_DEVICE = 1, UPD_HOST = 2, UPD_ATOMIC = 3 };
 struct upd_map {

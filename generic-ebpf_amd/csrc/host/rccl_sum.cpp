@@ -13,7 +13,7 @@
 #include <string>
 #include <vector>
 
-#include "internal.h"
+#include "runtime.h"
 
 namespace {
 

@@ -459,9 +459,9 @@ def test_one_launch_full_size_overwrite(gpu, env, cfg):
 
 
 def test_many_streams_separate_histograms(gpu, env):
-    """More concurrent streams (8) than the library's 4 pooled histogram row buffers, each
-    launching into its own histogram with no synchronisation between launches: the row buffers
-    are handed across streams with GPU-side waits, and every histogram must come out exact."""
+    """Eight concurrent streams, each launching into its own histogram with no synchronisation
+    between launches: every stream has its own row buffer (the pool holds 64 slots per device,
+    so none is handed from one stream to another here), and every histogram must come out exact."""
     import torch
     from generic_ebpf_amd import workloads
     lay = workloads.prog_c4()

@@ -255,6 +255,50 @@ def test_device_readback_vs_oracle(gpu, env, variant, layout, case):
         assert ex == "hip"
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("case,variant,sizes", [("stores17", 0, (256, 4096, 256, 65536)),
+                                                ("readback120", 1, (256, 4096))])
+def test_device_scratch_grows_in_flight(gpu, env, case, variant, sizes):
+    """Resident batches of growing size back to back on one stream, with no synchronisation (a
+    side stream: the tests before this one grew the current stream's buffers): the stream's write
+    log (stores17) and its spilled overlay (readback120, portable interpreter) are replaced by
+    larger ones while the batches before are still in flight.  The map and every batch's results
+    equal the oracle's run of the batches one after the other."""
+    import torch
+    mk, vs, me = (mw.CASES.get(case) or mw.READBACK[case])
+    lay = mk()
+    init = _init(vs, me, 51)
+    pks = [mw.packets(n, 52 + i) for i, n in enumerate(sizes)]
+    wants, state = [], init
+    for pk in pks:
+        ret, wf, state = _oracle(lay, vs, me, state, pk.reshape(-1), len(pk), 64)
+        assert not wf.any()
+        wants.append(ret)
+    m = gpu.Map(env, me, vs)
+    m.fill(init)
+    p = gpu.Prog(env, lay.patched([m.handle]))
+    try:
+        gpu.set_variant(variant)
+        dev = torch.device("cuda:0")
+        d_pks = [torch.from_numpy(np.ascontiguousarray(pk.reshape(-1))).to(dev) for pk in pks]
+        rets = [torch.zeros(len(pk), dtype=torch.int64, device=dev) for pk in pks]
+        flts = [torch.zeros(len(pk), dtype=torch.uint8, device=dev) for pk in pks]
+        stream = torch.cuda.Stream()
+        torch.cuda.synchronize()
+        for d_pk, d_ret, d_flt in zip(d_pks, rets, flts):
+            p.run_batch_dev(0, d_pk.data_ptr(), len(d_ret), 64, d_ret.data_ptr(), None,
+                            d_flt.data_ptr(), None, stream.cuda_stream)
+        torch.cuda.synchronize()
+        for d_ret, d_flt, want in zip(rets, flts, wants):
+            assert not d_flt.cpu().numpy().any()
+            np.testing.assert_array_equal(d_ret.cpu().numpy().view(np.uint64), want)
+        assert b"".join(m.lookup(k)[1] for k in range(me)) == state
+    finally:
+        gpu.set_variant(0)
+        p.destroy()
+        m.destroy()
+
+
 # ---- the same read-back programs over a hashtable (the spilled overlay on a table's values) ----
 
 def _hash_items(vs, seed, present=12):
