@@ -271,7 +271,11 @@ launch(struct ebpf_prog *ep, dprog_device *dp, const dp_launch &L0, hipStream_t 
 	// if a code object cannot be loaded — never a silent fallback)
 	enum { COMPILED, ASM_INTERP, HIP_INTERP } path = HIP_INTERP;
 	const int variant = g_variant.load();
-	const int mode = (L0.offsets == nullptr && L0.stride == 64 && !ep->xlated->asm_needs_general) ? 1 : 0;
+	// the staged kernel reads its packets with LDS-DMA, 16 bytes a lane: only a 16-byte-aligned
+	// base takes it (ebpf_gpu.h ebpf_prog_run_batch_dev); any other runs the general kernel
+	const bool aligned = (reinterpret_cast<uintptr_t>(L0.data) & 15) == 0;
+	const int mode =
+	    (L0.offsets == nullptr && L0.stride == 64 && aligned && !ep->xlated->asm_needs_general) ? 1 : 0;
 	int err;
 	// an overlay larger than the lanes keep on chip: the portable interpreter, spilled
 	const bool spill = ep->xlated->vstore_overlay && ep->xlated->ovl_entries > DP_OVL_MAX;

@@ -110,14 +110,13 @@ struct Translator {
 	// which counts the jump and continues at the target's entry (resolved in run()).
 	uint32_t loop_edge(uint64_t idx)
 	{
+		// (a jump before slot 0 wraps: past the program, not a state key, and not a loop — it
+		// faults when taken, so nothing is counted and has_loops stays as it is)
+		if (idx >= nslots)
+			return fault(EBPF_FAULT_SLOT);
 		const uint32_t id = new_entry();
 		out.entries[id].kind = DK_LOOPCNT;
 		out.has_loops = true;
-		if (idx >= nslots) { // (a jump before slot 0 wraps: past the program, not a state key)
-			const uint32_t f = fault(EBPF_FAULT_SLOT);
-			out.entries[id].next = f;
-			return id;
-		}
 		loop_next.push_back({id, key(idx, 0)});
 		return id;
 	}

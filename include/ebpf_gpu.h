@@ -147,7 +147,10 @@ enum ebpf_fault {
  * (flags & EBPF_BATCH_EXTENTS): packet i occupies [data + offsets[2i], data + offsets[2i+1]) —
  * offsets has 2*count entries, start <= end, packets in any order, with gaps between them or
  * overlapping (a capture's records in place: ebpf_pcap_extents).  A program that stores into
- * overlapping packets leaves their common bytes unspecified. */
+ * overlapping packets leaves their common bytes unspecified.  Offsets are 64-bit and may lie
+ * 4 GiB or more from data; a packet is shorter than 4 GiB: in both offsets modes an end below
+ * its start, or 2^32 bytes or more past it, gives a packet of length 0 (every load from it
+ * faults EBPF_FAULT_MEM). */
 struct ebpf_pkt_batch {
 	const void *data;
 	const uint64_t *offsets;
@@ -242,7 +245,11 @@ int ebpf_batch_wait(struct ebpf_batch_job *job, struct ebpf_batch_stats *stats);
  * hist_dev) is device memory on `device`.  Enqueued on `stream` (hipStream_t, NULL = default
  * stream) and returns without synchronising.  faults_dev / hist_dev may be NULL; hist_dev is
  * EBPF_HIST_BINS u64 counters that the kernel ADDS to (zero it yourself), or, with
- * EBPF_BATCH_HIST_OVERWRITE in batch->flags, sets to this batch's counts. */
+ * EBPF_BATCH_HIST_OVERWRITE in batch->flags, sets to this batch's counts.
+ * batch->data may have any alignment.  The staged kernel for fixed 64-byte packets reads them
+ * 16 bytes a lane, so it runs only when data is 16-byte aligned; a 64-byte-stride batch on any
+ * other base runs on the general kernel (ebpf_dexec_info.layout 0; same results).  ret_dev and
+ * batch->offsets must be 8-byte aligned, as their types say. */
 int ebpf_prog_run_batch_dev(struct ebpf_prog *ep, int device, const struct ebpf_pkt_batch *batch,
 			    uint64_t *ret_dev, uint8_t *faults_dev, uint64_t *hist_dev,
 			    void *stream);

@@ -1470,9 +1470,9 @@ std_succ(const struct oracle_prog *p, uint64_t pc, uint64_t succ[2], int *back)
 	if (op == 0x05) {
 		if (off == -1)
 			return 0;
-		*back = off < 0;
 		if (target < 0)
-			return 0;
+			return 0; /* F_SLOT when taken: it leaves the program, no loop */
+		*back = off < 0;
 		succ[0] = (uint64_t)target;
 		return 1;
 	}

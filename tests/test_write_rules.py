@@ -2,8 +2,8 @@
 from the program's own bytecode in the translator and, independently, in the oracle:
 
 * a program "loops" when a backward jump is reachable from slot 0 — an unreachable one does not
-  count, nor does JA -1 (it spins: EBPF_FAULT_LOOP), nor a conditional jump whose target lies
-  before slot 0 (EBPF_FAULT_SLOT);
+  count, nor does JA -1 (it spins: EBPF_FAULT_LOOP), nor a jump, conditional or JA, whose target
+  lies before slot 0 (EBPF_FAULT_SLOT when taken);
 * a loop "reads its counters back" when a counter idiom's register is live after its STX on the
   slot graph, where a CALL reads only its helper's arguments (lookup r1-r2, update r1-r4);
 * a loop-free program with more than 16 stores it reads back needs more overlay words than the
@@ -55,6 +55,28 @@ def prog_cond_before_start():
     at = len(b) // 8 - 2
     b[8 * at + 2:8 * at + 4] = (-(at + 5) & 0xffff).to_bytes(2, "little")
     return bytes(b), rel
+
+
+def _ja_before_start(code, at):
+    """slot `at` (a JA) retargeted to 4 slots before slot 0"""
+    b = bytearray(code)
+    assert b[8 * at] == 0x05
+    b[8 * at + 2:8 * at + 4] = (-(at + 5) & 0xffff).to_bytes(2, "little")
+    return bytes(b)
+
+
+def prog_ja_before_start_untaken():
+    """20 stores, r0 = 7, exit; a backward JA to before slot 0 on a branch no packet takes (r0 is
+    the hit's value pointer, never 0) but which is reachable on the slot graph"""
+    code, rel = stdprogs.asm(_hit_then([I("jeq_imm", 0, imm=0, off="bad"), I("mov64_imm", 0, imm=7),
+                                        I("exit"), ("label", "bad"), I("ja", off=0)]))
+    return _ja_before_start(code, len(code) // 8 - 1), rel
+
+
+def prog_ja_before_start_taken():
+    """20 stores, then a JA to before slot 0"""
+    code, rel = stdprogs.asm(_hit_then([I("ja", off=0), I("exit")]))
+    return _ja_before_start(code, len(code) // 8 - 2), rel
 
 
 def prog_walk_counters(call):
@@ -168,6 +190,27 @@ def test_oracle_jump_before_slot_0_is_no_loop():
     assert (flt == F_SLOT).all() and after[0] == _maps(6)[0][2]
 
 
+def test_oracle_untaken_ja_before_slot_0_is_no_loop():
+    """a reachable backward JA that leaves the program is no loop: the 20 stores all land (a
+    program held to be looping faults EBPF_FAULT_WRITES at the 17th)"""
+    pk = walk_packets(200, 13)
+    ret, flt, after = _oracle(*prog_ja_before_start_untaken(), _maps(14), pk)
+    assert not flt.any() and (ret == 7).all()
+    init = bytearray(_maps(14)[0][2])
+    for p in pk:   # as in test_oracle_unreachable_backward_jump_is_no_loop
+        k = int(p[0]) & 15
+        init[8 * k:8 * k + 8] = bytes([16, 17, 18, 19, 12, 13, 14, 15])
+    assert after[0] == bytes(init)
+
+
+def test_oracle_taken_ja_before_slot_0_faults_slot():
+    """the JA taken after 20 stores: EBPF_FAULT_SLOT (not WRITES at the 17th store), and a
+    packet that faults leaves no store behind"""
+    pk = walk_packets(100, 15)
+    ret, flt, after = _oracle(*prog_ja_before_start_taken(), _maps(16), pk)
+    assert (flt == F_SLOT).all() and not ret.any() and after[0] == _maps(16)[0][2]
+
+
 @pytest.mark.parametrize("call,limited", [("update", True), ("lookup", False)])
 def test_oracle_helper_arguments_decide_read_back(call, limited):
     pk = walk_packets(3000, 7)
@@ -244,6 +287,8 @@ CASES = {
     "unreachable_back": (prog_unreachable_back, False),
     "ja_self": (prog_ja_self, False),
     "cond_before_start": (prog_cond_before_start, False),
+    "ja_before_start_untaken": (prog_ja_before_start_untaken, False),
+    "ja_before_start_taken": (prog_ja_before_start_taken, False),
     "walk_update": (lambda: prog_walk_counters("update"), True),
     "walk_lookup": (lambda: prog_walk_counters("lookup"), True),
 }
