@@ -3,7 +3,8 @@
 
 Output: <out>.s (the code object source: two interpreter kernels sharing one handler set, the
 handler linker kernel, the handler offset table) and <out>.h (handler family ids for the host
-lowering in asm_runtime.cpp).
+lowering in asm_runtime.cpp, and the ABI the kernels share with the host: kernel-argument
+offsets, registers, flag bits, the template table's order — see "the ABI shared with the host").
 
 Execution model (one lane = one packet, wavefront-lockstep dispatch):
   * eBPF register rK lives in v[2K:2K+1] (VGPRs, never memory);
@@ -45,10 +46,14 @@ V_T = 41             # parked entry byte offset
 V_STK = 42           # lane stack bottom (LDS byte address)
 V_L16 = 43           # staged image: lane * 16 (LDS-DMA staging offset)
 V_IDX = 43           # general image: the lane's packet index in the launch
+V_RES = 44           # v[44:45]: r0 of the lanes that retired in the running group
 # v[44:45] (RETK == 1) or v[64:64+2*RETK]: r0 of the lanes that retired, per group of the
 # current superblock (stored together at the start of the next superblock)
 H = [46, 47, 48, 49, 50, 51]         # handler temporaries
 R = list(range(52, 63))              # routine temporaries
+V_GIDX = H[3]        # at a group's start: the lanes' packet indices in the launch (the start
+                     # block of a compiled program reads them, asm_cc.cpp cc_prologue)
+V_HVAL = H[4]        # v[50:51] after .Lr_hlookup: the found slot's first 8 value bytes
 V_SEL = 63                           # v_perm selector 0x00010203 (byte swap)
 # Results of RETK consecutive groups are kept in VGPRs and written as one RETK x 512-B burst
 # (RETK > 1 adds 2*RETK VGPRs at v64).  Each wave walks superblocks of RETK consecutive groups.
@@ -104,11 +109,12 @@ S_OK = 62            # s[62:63] check: accumulated ok lanes
 S_REC = 64           # s[64:71] map record {handle, dev_base, value_size, max_entries, lds_off, pad}
 S_PREVG = 72         # group whose results are still in V_RET (-1: none)
 S_KMASK = 73         # superblock size - 1 of this launch (K' <= RETK, a power of two; host-chosen,
-                     # dp_launch.total_waves bits 28..29 = log2 K'): small batches use shorter
-                     # superblocks so that every wave gets work
+                     # dp_launch.total_waves from WAVES_SB_SHIFT up = log2 K'): small batches use
+                     # shorter superblocks so that every wave gets work
 S_WAVE = 3
-NSGPR = 76           # + VCC, XNACK, FLAT_SCRATCH; s[74:75]: compiled programs' short-lane mask
-                     # in the general image (asm_cc.cpp ldxpkc_general)
+S_SHORT = 74         # s[74:75], general image: compiled programs' short-lane mask (asm_cc.cpp
+                     # ldxpkc_general)
+NSGPR = 76           # + VCC, XNACK, FLAT_SCRATCH
 # general image: s[76:77] = the run mask of a compiled program's hoisted packet loads (asm_cc.cpp
 # runmask: the running lanes whose packet holds every load of the run)
 S_RUNMASK = 76
@@ -230,15 +236,108 @@ for z in (4, 8):
 # address leaves the packet take the generic path (s[10:11] = the offset)
 for z in SIZES:
     fam("LDXPKTV%d" % z, 2)
-LOOP_BUDGET = 1 << 20          # dprog.h DP_LOOP_BUDGET
-# the lane's stack slice below the frame (dprog.h DP_OVL_*): loop count, overlay count, the
-# scratch a store into a map value is redirected to, the overlay entries
-OVL_COUNT, VST_SCRATCH, WCOUNT, OVL_ENTRIES = 4, 8, 16, 24
-WRITES_MAX = 16             # dprog.h DP_WRITES_MAX (dp_launch.vflags bit 4, DP_VF_WCAP)
-FAULT_WRITES = 11           # include/ebpf_gpu.h EBPF_FAULT_WRITES
-WPHASE_OFF = 0xd0              # dp_launch.wphase (store_phased)
-VFLAGS_OFF = 0xcc              # dp_launch.vflags: bit 0 overlay, bit 1 value stores provided for
 SPILL = 51                     # v51 (H[5]): .Lr_check's SGPR spill lanes around .Lr_vstore
+
+# ---------------------------------------------------------------- the ABI shared with the host
+# The kernels, the host that launches them (asm_runtime.cpp, gpu_runtime.cpp) and the host
+# compiler that encodes machine words running inside them (asm_cc.cpp, asm_jit.cpp) agree on the
+# kernel-argument layout, on registers, on flag bits and on a few constants.  This file states all
+# of them once and header_abi() writes them into asm_handlers.h:
+#   * registers (AH_S_*, AH_V_*), the mode bits (AH_MODE_*) and the template table's order
+#     (AH_JT_*) are this file's to choose: the host names them and holds no copy;
+#   * layouts and values that dprog.h / ebpf_gpu.h declare for all the device code (dp_launch,
+#     dp_map, dp_entry, DP_*, EBPF_FAULT_WRITES) are copied here, exported (AH_L_*, AH_M_*,
+#     AH_E_*, AH_DP_*, AH_EBPF_FAULT_WRITES) and asserted equal to the declarations in
+#     asm_runtime.cpp, entry by entry through the lists AH_LAUNCH_FIELDS / AH_SHARED_VALUES
+#     (dprog.h cannot include a generated header: the HIP sources include it).  A copy that
+#     drifts stops the build there.
+
+# dp_launch fields the kernels load: name -> (byte offset, bytes), and the kernarg size
+LAUNCH = {
+    "prog": (0x00, 8), "maps": (0x08, 8), "data": (0x10, 8), "offsets": (0x18, 8),
+    "off_base": (0x20, 8), "ret": (0x28, 8), "faults": (0x30, 8), "hist": (0x38, 8),
+    "count": (0x40, 8), "stride": (0x48, 4), "start": (0x4c, 4), "nmaps": (0x50, 4),
+    "nentries": (0x54, 4), "stack_stride": (0x58, 4), "lds_stack_base": (0x5c, 4),
+    "total_waves": (0x60, 4), "lds_pkt_base": (0x64, 4), "hist_rows": (0x68, 8),
+    "hist_user": (0x70, 8), "hist_flags": (0x78, 4), "nwg": (0x7c, 4),
+    "upd_log": (0x80, 8), "upd_cap": (0x88, 4), "upd_stride": (0x8c, 4), "pkt_base": (0x90, 8),
+    "upd_faulted": (0xa8, 8), "vflags": (0xcc, 4), "wphase": (0xd0, 4),
+}
+KERNARG_BYTES = 232
+# ebpf_asm_link's arguments (asm_runtime.cpp asm_link_args)
+LINK_ARGS = {"entries": (0x0, 8), "count": (0x8, 4)}
+LINK_KERNARG_BYTES = 16
+
+
+def karg(*fields, table=LAUNCH):
+    """The kernel-argument operand of an s_load that starts at the first of `fields`; a wider
+    load names every field it covers, which must lie back to back."""
+    off, size = table[fields[0]]
+    end = off + size
+    for f in fields[1:]:
+        assert table[f][0] == end, "%s does not follow at 0x%x" % (f, end)
+        end += table[f][1]
+    return "s[0:1], 0x%x" % off
+
+
+def karg_regs(*pairs):
+    """karg() of a load into consecutive SGPRs, [(field, the SGPR it must land in), ...]."""
+    (f0, r0) = pairs[0]
+    for f, r in pairs:
+        assert r == r0 + (LAUNCH[f][0] - LAUNCH[f0][0]) // 4, "%s is not loaded into s%d" % (f, r)
+    return karg(*[f for f, _ in pairs])
+
+
+# dp_map (a record is loaded whole into s[S_REC:S_REC+7]) and the lowered dp_entry (into
+# s[S_ENT:S_ENT+7]; aux0 / aux1 are the two operand words asm_runtime.cpp set_aux writes)
+MAP_REC = {"handle": 0, "dev_base": 8, "value_size": 16, "max_entries": 20, "lds_off": 24, "flags": 28}
+MAP_REC_BYTES = 32
+ENTRY = {"handler": 0, "imm": 8, "next": 16, "target": 20, "aux0": 24, "aux1": 28}
+ENTRY_BYTES = 32
+
+# the mode word s7: what kind of kernel and launch this is, set once at kernel start
+S_MODE = 7
+MODE_STAGED = 0        # staged 64-B packets (else the general kernels)
+MODE_JIT = 1           # a compiled program: V_T holds code offsets, not entry offsets
+MODE_STRUCTURED = 2    # ... with structured control flow (set by its prologue, asm_cc.cpp)
+MODE_HDRSTAGE = 3      # general kernels: header staging (PKTLDS_HDRSTAGE)
+MODE_OVERLAY = 13      # VF_OVERLAY
+MODE_KEEP = 14         # keep mode (VF_KEEP), general kernels: PKTLDS_HDRKEEP
+MODE_EXTENTS = 15      # VF_EXTENTS
+
+
+def mode_test(bit):
+    return "s_bitcmp1_b32 %s, %d" % (s(S_MODE), bit)
+
+
+def mode_set(bit):
+    return "s_or_b32 %s, %s, %s" % (s(S_MODE), s(S_MODE), "%d" % (1 << bit) if bit < 4 else "0x%x" % (1 << bit))
+
+
+# dp_launch.vflags bits (dprog.h DP_VF_*)
+VF_OVERLAY = 0         # the program reads its own stores into map values
+VF_VSTORE = 1          # it has value-store sites
+VF_EXTENTS = 2         # offsets holds (start, end) pairs
+VF_KEEP = 3            # staged kernels keep the group's packets in LDS (LDXPKTV)
+VF_WCAP = 4            # count each packet's logged writes
+VF_ENTRIES_SHIFT, VF_ENTRIES_BITS = 8, 8     # the overlay's entries per lane
+# dp_launch.lds_pkt_base bits above the LDS offset (general kernels)
+PKTLDS_HDRSTAGE = 31   # stage packet headers into v22..v37
+PKTLDS_HDRKEEP = 30    # ... and keep them in the wave's LDS packet buffer
+# dp_launch.total_waves: log2 of the superblock size above the wave count
+WAVES_SB_SHIFT = 28
+# dp_launch.hist_flags
+HIST_STORE = 0         # the last workgroup stores the reduced histogram instead of adding it
+# dp_launch.wphase (store_phased): window | log2(period) << 16, bit 31 = the wide kernel's 16 slots
+WPHASE_PERIOD_SHIFT = 16
+WPHASE_WIDE = 31
+
+LOOP_BUDGET = 1 << 20          # DP_LOOP_BUDGET
+# the lane's stack slice below the frame (DP_OVL_*, DP_WCOUNT): loop count, overlay count, the
+# scratch a store into a map value is redirected to, the write count, the overlay entries
+OVL_COUNT, VST_SCRATCH, WCOUNT, OVL_ENTRIES = 4, 8, 16, 24
+WRITES_MAX = 16                # DP_WRITES_MAX (VF_WCAP)
+FAULT_WRITES = 11              # EBPF_FAULT_WRITES
 
 
 def variants(arity):
@@ -562,7 +661,7 @@ def h_ldx_pkt_staged(z, d):
 def h_ldx_pkt_const(z, d, off):
     """Packet load at a translation-time byte offset from the packet bytes held in v22..v37,
     so 1-2 VALU (bit-field extract / byte align), no indexing.  Staged kernels: every packet is
-    exactly 64 bytes.  General kernels (header staging, s7 bit 3): lanes whose packet is shorter
+    exactly 64 bytes.  General kernels (header staging, MODE_HDRSTAGE): lanes whose packet is shorter
     than off + z fault MEM, lanes shorter than 64 bytes (not staged) load from memory."""
     if off + z > 64:
         return []          # never selected: the lowering faults such loads statically
@@ -733,11 +832,11 @@ def gather(a0, acc, tmp, z, tag=None):
 
 
 def vflags_test(bit, skip):
-    """Branches to `skip` when dp_launch.vflags bit `bit` is clear (bit 0, the overlay: s7 bit 13,
+    """Branches to `skip` when dp_launch.vflags bit `bit` is clear (VF_OVERLAY: MODE_OVERLAY,
     copied at kernel start; other bits: loaded, clobbering S_T3)."""
-    if bit == 0:
-        return ["s_bitcmp1_b32 s7, 13", "s_cbranch_scc0 %s" % skip]
-    return ["s_load_dword %s, s[0:1], 0x%x" % (s(S_T3), VFLAGS_OFF),
+    if bit == VF_OVERLAY:
+        return [mode_test(MODE_OVERLAY), "s_cbranch_scc0 %s" % skip]
+    return ["s_load_dword %s, %s" % (s(S_T3), karg("vflags")),
             "s_waitcnt lgkmcnt(0)",
             "s_bitcmp1_b32 %s, %d" % (s(S_T3), bit),
             "s_cbranch_scc0 %s" % skip]
@@ -746,13 +845,13 @@ def vflags_test(bit, skip):
 def h_ldx_gen(z, d, sr):
     """Generic load: address = r_src + sext(off) (s[10:11]); region check, then byte-wise
     flat loads (packet/map in global memory, stack in LDS via the shared aperture); a program
-    that reads its own stores into map values (dp_launch.vflags bit 0) then takes the bytes it
-    stored from its overlay (.Lr_ovlfix)."""
+    that reads its own stores into map values (dp_launch.vflags VF_OVERLAY) then takes the bytes
+    it stored from its overlay (.Lr_ovlfix)."""
     a0 = H[0]
     out = ["v_lshl_add_u64 %s, s[10:11], 0, %s" % (vp(a0), pair(sr)),
            "s_mov_b32 %s, %d" % (s(S_T0), z), "s_mov_b32 %s, 0" % s(S_T1)] + call(".Lr_check")
     out += gather(a0, (H[2], H[3]), [H[4]] + R[:7], z, "{uid}")
-    out += vflags_test(0, ".Lnovl_{uid}") + call(".Lr_ovlfix") + [".Lnovl_{uid}:"]
+    out += vflags_test(VF_OVERLAY, ".Lnovl_{uid}") + call(".Lr_ovlfix") + [".Lnovl_{uid}:"]
     out += ["v_mov_b32 %s, %s" % (lo(d), v(H[2])), "v_mov_b32 %s, %s" % (hi(d), v(H[3]))]
     return out
 
@@ -827,17 +926,17 @@ def h_ldx_pktv(z, d, sr):
             "s_cbranch_scc0 .Lpv_gen_{uid}"]
     A, B = v(H[4]), v(H[5])
     if STAGED_IMAGE:
-        # keep mode (s7 bit 14): the group's packets stay in the wave's LDS packet buffer while
+        # keep mode (MODE_KEEP): the group's packets stay in the wave's LDS packet buffer while
         # the program runs, transposed (lds_pkt_dwords), so read them there
-        out += ["s_bitcmp1_b32 s7, 14",
+        out += [mode_test(MODE_KEEP),
                 "s_cbranch_scc0 .Lpv_flat_{uid}",
                 "v_lshrrev_b32 %s, 2, v%d" % (A, V_L16),
                 "v_add_u32 %s, %s, %s" % (A, s(S_PKTLDS), A)]
     else:
-        # general kernels with the headers kept in LDS (s7 bit 14, every lane's first 64 bytes,
+        # general kernels with the headers kept in LDS (MODE_KEEP, every lane's first 64 bytes,
         # transposed, when its packet is at least that long): when every running lane's bytes
         # lie in its first 64 and its packet has them staged, read them there
-        out += ["s_bitcmp1_b32 s7, 14",
+        out += [mode_test(MODE_KEEP),
                 "s_cbranch_scc0 .Lpv_flat_{uid}",
                 "v_cmp_ge_u32_e64 vcc, %d, %s" % (64 - z, v(H[2])),
                 "s_and_b64 %s, vcc, exec" % sp(S_MASK),
@@ -1102,7 +1201,8 @@ def hprobe_body(tag):
           # the slot's first 8 value bytes (value offset 16 for keys of <= 8 bytes), same line:
           # lanes that meet their key here keep them in v[50:51] for the code generator's
           # forwarded value loads (asm_cc.cpp AHF_LDXHV)
-          "global_load_dwordx2 %s, %s, off offset:16%s" % (vp(H[4]), sa, PROBE_POLICY)] + probe_wait("hq" + T) + [
+          "global_load_dwordx2 %s, %s, off offset:16%s" % (vp(V_HVAL), sa, PROBE_POLICY)] + \
+        probe_wait("hq" + T) + [
           "v_cmp_eq_u32_e64 vcc, 0, %s" % v(R[6]),           # empty slot: not found
           "s_andn2_b64 %s, %s, vcc" % (sp(S_OK), sp(S_OK)),
           "v_cmp_eq_u32_e64 %s, %s, %s" % (sp(S_JUNK), v(R[7]), c),
@@ -1163,16 +1263,16 @@ def hprobe_body(tag):
 def log_record(T, word, ret):
     """For the lanes in exec: a slot in the launch's write log (one atomic add on its counter per
     wave), R[4:5] = the record's address (log + 64 + slot * stride), its first 16 bytes written:
-    {u64 packet index, u32 entry | map << 20, u32 `word`}.  With dp_launch.vflags bit 4
+    {u64 packet index, u32 entry | map << 20, u32 `word`}.  With dp_launch.vflags VF_WCAP
     (DP_VF_WCAP) every lane first counts the write in its stack slice (DP_WCOUNT): a packet's
     write past WRITES_MAX faults it EBPF_FAULT_WRITES instead.  A full log (the host sizes it for
     the program's most writes per path: a library bug) faults MEM, loudly, rather than lose a
     write; exec empty after that branches to `ret`.  Uses R[0:7], S_T0..2, S_MASK, S_JUNK,
     s[64:69]."""
     return [
-        "s_load_dword %s, s[0:1], 0x%x" % (s(S_T0), VFLAGS_OFF),
+        "s_load_dword %s, %s" % (s(S_T0), karg("vflags")),
         "s_waitcnt lgkmcnt(0)",
-        "s_bitcmp1_b32 %s, 4" % s(S_T0),
+        "s_bitcmp1_b32 %s, %d" % (s(S_T0), VF_WCAP),
         "s_cbranch_scc0 .Lwc_ok%s" % T,
         "v_add_u32 %s, %d, v%d" % (v(R[0]), WCOUNT, V_STK),
         "v_mov_b32 %s, 1" % v(R[1]),
@@ -1185,8 +1285,8 @@ def log_record(T, word, ret):
         "s_cbranch_execz %s" % ret,
         ".Lwc_ok%s:" % T,
         # a log slot per lane: one atomic add on the log's counter for the wave
-        "s_load_dwordx4 s[64:67], s[0:1], 0x80",         # upd_log, upd_cap, upd_stride
-        "s_load_dwordx2 s[68:69], s[0:1], 0x90",         # pkt_base
+        "s_load_dwordx4 s[64:67], %s" % karg("upd_log", "upd_cap", "upd_stride"),
+        "s_load_dwordx2 s[68:69], %s" % karg("pkt_base"),
         "s_waitcnt lgkmcnt(0)",
         "s_bcnt1_i32_b64 %s, exec" % s(S_T0),
         "v_mbcnt_lo_u32_b32 %s, exec_lo, 0" % v(R[0]),
@@ -1209,8 +1309,8 @@ def log_record(T, word, ret):
         "s_cbranch_scc1 .Lup_room%s" % T,
         "s_mov_b32 %s, 3" % s(S_CODE)] + call(".Lr_fault") + [
         "s_cbranch_execz %s" % ret,
-        "s_load_dwordx4 s[64:67], s[0:1], 0x80",
-        "s_load_dwordx2 s[68:69], s[0:1], 0x90",
+        "s_load_dwordx4 s[64:67], %s" % karg("upd_log", "upd_cap", "upd_stride"),
+        "s_load_dwordx2 s[68:69], %s" % karg("pkt_base"),
         "s_waitcnt lgkmcnt(0)",
         ".Lup_room%s:" % T,
         # the record: log + 64 + slot * stride
@@ -1308,8 +1408,8 @@ def ovl_store(T, nv):
     """Remember, in the lanes' overlays, the z = S_T0 bytes of nv (two VGPRs) stored at H[0:1]:
     for each of the (one or two) 8-byte words the store touches, its entry — made on first use
     with the word's batch-start bytes from the mirror — gets the bytes.  A lane whose overlay is
-    full (its entries = dp_launch.vflags bits 8..15; only a program with loops that reads its
-    counters back fills it, ebpf_gpu.h) when the store needs a new entry gets OVF = 1 and
+    full (its entries = dp_launch.vflags from VF_ENTRIES_SHIFT up; only a program with loops that
+    reads its counters back fills it, ebpf_gpu.h) when the store needs a new entry gets OVF = 1 and
     stores nothing more.  For the lanes in exec; clobbers R[0:3], R[8:10], H[2:4], S_T3,
     S_BYTES, S_MASK, S_JUNK (saved exec), vcc."""
     W0, W1, CNT, IDX, E, X, Y, OVF = R[0], R[1], R[2], R[3], R[8], H[2], H[3], R[9]
@@ -1360,9 +1460,9 @@ def ovl_store(T, nv):
               "v_cmp_eq_u32_e64 vcc, -1, %s" % v(IDX),
               "s_and_saveexec_b64 %s, vcc" % sp(S_MASK),
               "s_cbranch_execz .Los%s_have" % t,
-              "s_load_dword %s, s[0:1], 0x%x" % (s(S_T3), VFLAGS_OFF),
+              "s_load_dword %s, %s" % (s(S_T3), karg("vflags")),
               "s_waitcnt lgkmcnt(0)",
-              "s_bfe_u32 %s, %s, 0x80008" % (s(S_T3), s(S_T3)),
+              "s_bfe_u32 %s, %s, 0x%x" % (s(S_T3), s(S_T3), VF_ENTRIES_BITS << 16 | VF_ENTRIES_SHIFT),
               "v_cmp_le_u32_e64 vcc, %s, %s" % (s(S_T3), v(CNT)),
               "v_cndmask_b32_e64 %s, %s, 1, vcc" % (v(OVF), v(OVF)),
               "s_andn2_b64 exec, exec, vcc",
@@ -1412,21 +1512,21 @@ def vstore_routine():
       * kinds 2 and 3 read the value the packet sees there (L: the mirror's bytes under its
         overlay); kind 3 leaves L in the lane's scratch (the handler's own read-modify-write,
         pointed there, then fetches it); kind 2 adds X - L, kind 3 the addend;
-      * the overlay (dp_launch.vflags bit 0) remembers the stored value;
+      * the overlay (dp_launch.vflags VF_OVERLAY) remembers the stored value;
       * an addition aligned to its width within the values of a DP_MAP_ATOMIC map goes into its
         delta area (a device atomic); everything else is a record in the batch's log
         {packet, map << 20 | DP_REC_VALUE | add << 16 | size, offset, data, hashtable slot}.
     Returns S_JUNK = the lanes to fault (code S_CODE): the log full, or value stores not provided
-    for (vflags bit 1 clear: the translator saw none).  Preserves S_T0..S_T2 and v51 (SPILL);
+    for (vflags VF_VSTORE clear: the translator saw none).  Preserves S_T0..S_T2 and v51 (SPILL);
     clobbers R[*], H[2:4], S_T3, S_BYTES, S_MASK, s[64:71], vcc."""
     L_, NV, OFF, VOFF, SLOT, WORD, ADD = (R[4], R[5]), (R[6], R[7]), R[0], R[2], R[3], R[8], R[10]
     L = [".Lr_vstore:",
          "v_writelane_b32 v%d, %s, 11" % (SPILL, s(S_LINK)),
          "v_writelane_b32 v%d, %s, 12" % (SPILL, s(S_LINK + 1)),
          "s_mov_b64 %s, 0" % sp(S_JUNK),
-         "s_load_dword %s, s[0:1], 0x%x" % (s(S_T3), VFLAGS_OFF),
+         "s_load_dword %s, %s" % (s(S_T3), karg("vflags")),
          "s_waitcnt lgkmcnt(0)",
-         "s_bitcmp1_b32 %s, 1" % s(S_T3),
+         "s_bitcmp1_b32 %s, %d" % (s(S_T3), VF_VSTORE),
          "s_cbranch_scc1 .Lvs_go",
          "s_mov_b64 %s, exec" % sp(S_JUNK),
          "s_mov_b32 %s, 9" % s(S_CODE),          # EBPF_FAULT_MAP_WRITE
@@ -1434,7 +1534,7 @@ def vstore_routine():
          ".Lvs_go:",
          "s_cmp_eq_u32 %s, 1" % s(S_T1),
          "s_cbranch_scc1 .Lvs_plain"] + gather(H[0], L_, H[4], None, "vs") + \
-        vflags_test(0, ".Lvs_noovl") + ovl_fix("vs", L_) + [
+        vflags_test(VF_OVERLAY, ".Lvs_noovl") + ovl_fix("vs", L_) + [
          ".Lvs_noovl:",
          "s_cmp_eq_u32 %s, 3" % s(S_T1),
          "s_cbranch_scc0 .Lvs_cnt",
@@ -1456,7 +1556,7 @@ def vstore_routine():
          "v_mov_b32 %s, %s" % (v(NV[1]), v(H[3])),
          "v_mov_b32 %s, 0" % v(L_[0]),
          "v_mov_b32 %s, 0" % v(L_[1]),
-         ".Lvs_have:"] + vflags_test(0, ".Lvs_noovl2") + ovl_store("vs", NV) + [
+         ".Lvs_have:"] + vflags_test(VF_OVERLAY, ".Lvs_noovl2") + ovl_store("vs", NV) + [
          # (ovl_store kept exec there) lanes whose overlay was full fault WRITES, with nothing
          # of this store done
          "v_cmp_ne_u32_e64 %s, 0, %s" % (sp(S_JUNK), v(R[9])),
@@ -1528,12 +1628,12 @@ def vstore_routine():
          "s_andn2_b64 exec, %s, exec" % sp(S_MASK),                # the lanes left: records
          ".Lvs_rec:",
          "s_cbranch_execz .Lvs_ret",
-         # capped writes (vflags bit 4, DP_VF_WCAP): every record (the lanes here: a DP_MAP_ATOMIC
+         # capped writes (vflags VF_WCAP): every record (the lanes here: a DP_MAP_ATOMIC
          # map's additions went to its delta area above) counts in the lane's slice; the one past
          # WRITES_MAX faults
-         "s_load_dword %s, s[0:1], 0x%x" % (s(S_T3), VFLAGS_OFF),
+         "s_load_dword %s, %s" % (s(S_T3), karg("vflags")),
          "s_waitcnt lgkmcnt(0)",
-         "s_bitcmp1_b32 %s, 4" % s(S_T3),
+         "s_bitcmp1_b32 %s, %d" % (s(S_T3), VF_WCAP),
          "s_cbranch_scc0 .Lvs_wc_ok",
          "s_mov_b64 %s, exec" % sp(S_MASK),
          "v_add_u32 %s, %d, v%d" % (v(R[1]), WCOUNT, V_STK),
@@ -1559,8 +1659,8 @@ def vstore_routine():
          "v_cndmask_b32 %s, %s, %s, vcc" % (v(L_[0]), v(NV[0]), v(L_[0])),
          "v_cndmask_b32 %s, %s, %s, vcc" % (v(L_[1]), v(NV[1]), v(L_[1])),
          # a log slot per lane: one atomic add on the log's counter for the wave
-         "s_load_dwordx4 s[64:67], s[0:1], 0x80",                # upd_log, upd_cap, upd_stride
-         "s_load_dwordx2 s[68:69], s[0:1], 0x90",                # pkt_base
+         "s_load_dwordx4 s[64:67], %s" % karg("upd_log", "upd_cap", "upd_stride"),
+         "s_load_dwordx2 s[68:69], %s" % karg("pkt_base"),
          "s_waitcnt lgkmcnt(0)",
          "s_cmp_eq_u64 s[64:65], 0",
          "s_cbranch_scc0 .Lvs_log",
@@ -1901,7 +2001,7 @@ def routines():
           "v_readlane_b32 s6, v%d, %s" % (V_T, s(S_T0)),
           "v_cmp_eq_u32_e64 %s, s6, v%d" % (sp(S_MASK), V_T),
           "s_and_b64 exec, %s, %s" % (sp(S_MASK), sp(S_ALIVE)),
-          "s_bitcmp1_b32 s7, 1",
+          mode_test(MODE_JIT),
           "s_cbranch_scc1 .Lsched_jit",
           "s_load_dwordx8 s[8:15], s[%d:%d], s6" % (S_PROG, S_PROG + 1),
           "s_waitcnt lgkmcnt(0)",
@@ -1953,8 +2053,8 @@ def routines():
           "ds_add_u32 %s, %s" % (v(R[8]), v(R[9])),
           ".Lex_nohist:",
           "s_andn2_b64 %s, %s, exec" % (sp(S_ALIVE), sp(S_ALIVE)),
-          # structured compiled programs (s7 bit 2) call the exit and continue themselves
-          "s_bitcmp1_b32 s7, 2",
+          # structured compiled programs (MODE_STRUCTURED) call the exit and continue themselves
+          mode_test(MODE_STRUCTURED),
           "s_cbranch_scc0 .Lex_sched",
           "s_setpc_b64 %s" % sp(S_LINK),
           ".Lex_sched:"] + goto(".Lr_schedule")
@@ -1971,8 +2071,8 @@ def routines():
           ".Lfl_nofault:",
           # a program with map writes: the packet's bit in dp_launch.upd_faulted (its logged
           # writes do not land; map_writes.hip)
-          "s_load_dwordx2 %s, s[0:1], 0xa8" % sp(S_JUNK),
-          "s_load_dword %s, s[0:1], 0x90" % s(S_BYTES),            # pkt_base (low word)
+          "s_load_dwordx2 %s, %s" % (sp(S_JUNK), karg("upd_faulted")),
+          "s_load_dword %s, %s" % (s(S_BYTES), karg("pkt_base")),   # (low word)
           "s_waitcnt lgkmcnt(0)",
           "s_cmp_eq_u64 %s, 0" % sp(S_JUNK),
           "s_cbranch_scc1 .Lfl_nomark"] + lane_pkt_index(R[9]) + [
@@ -2000,7 +2100,7 @@ def routines():
           "s_setpc_b64 %s" % sp(S_LINK),
           ".Lfl_none:",
           # structured compiled programs continue with no lane (their join restores the rest)
-          "s_bitcmp1_b32 s7, 2",
+          mode_test(MODE_STRUCTURED),
           "s_cbranch_scc0 .Lfl_sched",
           "s_setpc_b64 %s" % sp(S_LINK),
           ".Lfl_sched:"] + goto(".Lr_schedule")
@@ -2202,7 +2302,7 @@ def routines():
           "s_add_u32 %s, %s, 1" % (s(S_T2), s(S_T2)),
           "s_branch .Llk_map",
           ".Llk_done:",
-          "s_bitcmp1_b32 s7, 1",
+          mode_test(MODE_JIT),
           "s_cbranch_scc1 .Llk_jit"] + dispatch(12) + [
           ".Llk_jit:",     # compiled program: s12 = code offset of the next block
           "s_add_u32 %s, %s, s12" % (s(S_JUNK), s(S_CB)),
@@ -2213,7 +2313,7 @@ def routines():
     L += update_routine()
     L += hdelete_routine()
     L += vstore_routine()
-    # OVLFIX (called by generic loads when dp_launch.vflags bit 0): the packet's own stores over
+    # OVLFIX (called by generic loads when dp_launch.vflags VF_OVERLAY): the packet's own stores over
     # the S_T0 bytes at H[0:1] just read into H[2:3]
     L += [".Lr_ovlfix:"] + ovl_fix("L", (H[2], H[3])) + ["s_setpc_b64 %s" % sp(S_LINK)]
     # PREFETCH (staged kernel): LDS-DMA the 4 KB of 64-B packets of group s[S_T0] into this
@@ -2263,10 +2363,14 @@ def kernel(name, staged, jit=False):
     # v0 = workitem id; wave index within the 256-lane workgroup
     L += ["v_readfirstlane_b32 %s, v0" % s(S_WAVE),
           "s_lshr_b32 %s, %s, 6" % (s(S_WAVE), s(S_WAVE)),
-          "s_load_dwordx16 s[%d:%d], s[0:1], 0x0" % (S_PROG, S_PROG + 15),
-          "s_load_dwordx8 s[%d:%d], s[0:1], 0x40" % (S_COUNT, S_COUNT + 7),
-          "s_load_dword %s, s[0:1], 0x60" % s(S_GSTRIDE),
-          "s_load_dword %s, s[0:1], 0x64" % s(S_PKTLDS),
+          "s_load_dwordx16 s[%d:%d], %s" % (S_PROG, S_PROG + 15, karg_regs(
+              ("prog", S_PROG), ("maps", S_MAPS), ("data", S_DATA), ("offsets", S_OFFS),
+              ("off_base", S_OFFBASE), ("ret", S_RET), ("faults", S_FAULTS), ("hist", S_HIST))),
+          "s_load_dwordx8 s[%d:%d], %s" % (S_COUNT, S_COUNT + 7, karg_regs(
+              ("count", S_COUNT), ("stride", S_STRIDE), ("start", S_START), ("nmaps", S_NMAPS),
+              ("nentries", S_NENT), ("stack_stride", S_STKSTRIDE), ("lds_stack_base", S_LDSBASE))),
+          "s_load_dword %s, %s" % (s(S_GSTRIDE), karg("total_waves")),
+          "s_load_dword %s, %s" % (s(S_PKTLDS), karg("lds_pkt_base")),
           "s_mov_b64 %s, src_shared_base" % sp(S_SHARED),
           "v_mov_b32 v%d, 0x00010203" % V_SEL,
           # code base: routines are addressed relative to .Lcb
@@ -2279,51 +2383,48 @@ def kernel(name, staged, jit=False):
           "v_lshlrev_b32 v%d, 4, %s" % (V_L16, v(H[0])),
           "s_mov_b32 %s, -1" % s(S_PREVG),
           "s_waitcnt lgkmcnt(0)",
-          "s_mov_b32 s7, %d" % ((1 if staged else 0) | (2 if jit else 0)),
-          # s7 bit 13: the program reads its own stores into map values (dp_launch.vflags bit 0)
-          "s_load_dword %s, s[0:1], 0x%x" % (s(S_T3), VFLAGS_OFF)] + (
+          "s_mov_b32 %s, %d" % (s(S_MODE), (staged << MODE_STAGED) | (jit << MODE_JIT)),
+          # MODE_OVERLAY: the program reads its own stores into map values (VF_OVERLAY)
+          "s_load_dword %s, %s" % (s(S_T3), karg("vflags"))] + (
           # (the general kernels of a phased image leave write phasing off)
-          ["s_load_dword %s, s[0:1], 0x%x" % (s(S_WPHASE), WPHASE_OFF) if staged else
+          ["s_load_dword %s, %s" % (s(S_WPHASE), karg("wphase")) if staged else
            "s_mov_b32 %s, 0" % s(S_WPHASE),
            "s_mov_b32 %s, 0" % s(S_PEND)] if phased() else []) + [
           "s_waitcnt lgkmcnt(0)",
-          "s_bitcmp1_b32 %s, 0" % s(S_T3),
+          "s_bitcmp1_b32 %s, %d" % (s(S_T3), VF_OVERLAY),
           "s_cbranch_scc0 .L%s_noovl" % k,
-          "s_or_b32 s7, s7, 0x2000",
+          mode_set(MODE_OVERLAY),
           ".L%s_noovl:" % k,
-          # s7 bit 15: dp_launch.offsets holds (start, end) pairs (vflags bit 2, DP_VF_EXTENTS)
-          "s_bitcmp1_b32 %s, 2" % s(S_T3),
+          # MODE_EXTENTS: dp_launch.offsets holds (start, end) pairs (VF_EXTENTS)
+          "s_bitcmp1_b32 %s, %d" % (s(S_T3), VF_EXTENTS),
           "s_cbranch_scc0 .L%s_noext" % k,
-          "s_or_b32 s7, s7, 0x8000",
+          mode_set(MODE_EXTENTS),
           ".L%s_noext:" % k]
     if staged:
-        # s7 bit 14 (keep mode): the program reads its packet at run-time offsets from the LDS
+        # MODE_KEEP (keep mode): the program reads its packet at run-time offsets from the LDS
         # packet buffer (LDXPKTV), so the next group's DMA waits for the group's end.  Set by
-        # the host in dp_launch.vflags (DP_VF_KEEP, still in S_T3) for compiled and interpreted
+        # the host in dp_launch.vflags (VF_KEEP, still in S_T3) for compiled and interpreted
         # programs alike.  (Double-buffering the packets instead, two 4-KB buffers per wave,
         # measured slower on C3L: 0.294 against 0.284 ms, the LDS cutting 6 workgroups per CU
         # to 4; profiles/r05/keep2/)
-        L += ["s_bitcmp1_b32 %s, 3" % s(S_T3),
+        L += ["s_bitcmp1_b32 %s, %d" % (s(S_T3), VF_KEEP),
               "s_cbranch_scc0 .L%s_nokeep" % k,
-              "s_or_b32 s7, s7, 0x4000",
+              mode_set(MODE_KEEP),
               ".L%s_nokeep:" % k]
-    if not staged:   # header staging requested by the host (dp_launch.lds_pkt_base bit 31)
-        L += ["s_bitcmp1_b32 %s, 31" % s(S_PKTLDS),
+    if not staged:   # header staging requested by the host (dp_launch.lds_pkt_base PKTLDS_HDRSTAGE)
+        L += ["s_bitcmp1_b32 %s, %d" % (s(S_PKTLDS), PKTLDS_HDRSTAGE),
               "s_cbranch_scc0 .L%s_nogs" % k,
-              "s_or_b32 s7, s7, 8",
+              mode_set(MODE_HDRSTAGE),
               ".L%s_nogs:" % k,
-              # bit 30: the staged headers are kept in the wave's LDS packet buffer too, for the
-              # loads at run-time offsets (s7 bit 14 in the general kernels)
-              "s_bitcmp1_b32 %s, 30" % s(S_PKTLDS),
+              # PKTLDS_HDRKEEP: the staged headers are kept in the wave's LDS packet buffer too, for the
+              # loads at run-time offsets (MODE_KEEP in the general kernels)
+              "s_bitcmp1_b32 %s, %d" % (s(S_PKTLDS), PKTLDS_HDRKEEP),
               "s_cbranch_scc0 .L%s_nohl" % k,
-              "s_or_b32 s7, s7, 0x4000",
+              mode_set(MODE_KEEP),
               ".L%s_nohl:" % k,
-              "s_and_b32 %s, %s, 0x3fffffff" % (s(S_PKTLDS), s(S_PKTLDS))]
+              "s_and_b32 %s, %s, 0x%x" % (s(S_PKTLDS), s(S_PKTLDS), (1 << PKTLDS_HDRKEEP) - 1)]
     L += ["s_branch .Lprologue"]
     return L
-
-
-V_RES = 44   # v[44:45]: r0 of the lanes that retired in the running group
 
 
 def lane_index(dst):
@@ -2343,7 +2444,7 @@ def lane_pkt_index(dst):
 
 def pkt_setup(idx, tag):
     """General kernels: V_PKT / V_LEN of the running lanes' packets (index in VGPR idx), and with
-    header staging (s7 bit 3) their first 64 bytes into v22..v37.  Clobbers H[1], H[4:5], R[0],
+    header staging (MODE_HDRSTAGE) their first 64 bytes into v22..v37.  Clobbers H[1], H[4:5], R[0],
     R[2], S_JUNK; leaves exec = the running lanes (s[S_MASK] holds them meanwhile)."""
     return ["s_mov_b64 %s, exec" % sp(S_MASK),
             "s_cmp_eq_u64 %s, 0" % sp(S_OFFS),
@@ -2354,8 +2455,8 @@ def pkt_setup(idx, tag):
             "v_mov_b32 v%d, %s" % (V_LEN, s(S_STRIDE)),
             "s_branch .Lps_stage_%s" % tag,
             ".Lps_offsets_%s:" % tag,
-            # offsets[i], offsets[i + 1]; extents batches (s7 bit 15): offsets[2i], offsets[2i + 1]
-            "s_bitcmp1_b32 s7, 15",
+            # offsets[i], offsets[i + 1]; extents batches (MODE_EXTENTS): offsets[2i], offsets[2i + 1]
+            mode_test(MODE_EXTENTS),
             "s_cselect_b32 %s, 16, 8" % s(S_JUNK),
             "v_mov_b32 %s, %s" % (v(H[1]), s(S_JUNK)),
             "v_mad_u64_u32 %s, %s, v%d, %s, %s" % (vp(H[4]), sp(S_JUNK), idx, v(H[1]), sp(S_OFFS)),
@@ -2376,7 +2477,7 @@ def pkt_setup(idx, tag):
             # header staging: the first 64 bytes of every packet at least that long into
             # v22..v37 (what the staged kernels' LDS DMA provides)
             ".Lps_stage_%s:" % tag,
-            "s_bitcmp1_b32 s7, 3",
+            mode_test(MODE_HDRSTAGE),
             "s_cbranch_scc0 .Lps_done_%s" % tag,
             "v_cmp_lt_u32_e64 vcc, 63, v%d" % V_LEN,
             "s_and_b64 exec, %s, vcc" % sp(S_MASK),
@@ -2385,9 +2486,9 @@ def pkt_setup(idx, tag):
                                                                        V_PKT, V_PKT + 1, 16 * q)
             for q in range(4)] + [
             "s_waitcnt vmcnt(0)",
-            # (s7 bit 14: the headers also into the wave's LDS packet buffer, transposed, for
+            # (MODE_KEEP: the headers also into the wave's LDS packet buffer, transposed, for
             # loads at run-time offsets: h_ldx_pktv)
-            "s_bitcmp1_b32 s7, 14",
+            mode_test(MODE_KEEP),
             "s_cbranch_scc0 .Lps_done_%s" % tag,
             "v_mbcnt_lo_u32_b32 %s, -1, 0" % v(H[1]),
             "v_mbcnt_hi_u32_b32 %s, -1, %s" % (v(H[1]), v(H[1])),
@@ -2414,12 +2515,12 @@ def slot_commit():
     L = ["s_mov_b64 exec, -1",
          "s_and_b32 %s, %s, %s" % (s(S_BYTES), s(S_GROUP), s(S_KMASK))]
     if phased() and SLOTS == 16:
-        # wide phasing (dp_launch.wphase bit 31, the 96-VGPR kernel): 16 slots, the superblocks
+        # wide phasing (dp_launch.wphase WPHASE_WIDE, the 96-VGPR kernel): 16 slots, the superblocks
         # of a wave alternating between slots 0-7 and 8-15 (s98 bit 31 = the running half,
         # switched at each superblock's first group)
         L += ["s_cmp_eq_u32 %s, 0" % s(S_BYTES),
               "s_cbranch_scc0 .Lsc_half",
-              "s_bitcmp1_b32 %s, 31" % s(S_WPHASE),
+              "s_bitcmp1_b32 %s, %d" % (s(S_WPHASE), WPHASE_WIDE),
               "s_cbranch_scc0 .Lsc_half",
               "s_xor_b32 %s, %s, 0x80000000" % (s(S_PEND), s(S_PEND)),
               ".Lsc_half:",
@@ -2445,7 +2546,7 @@ def store_phased(tag, final):
     100-MHz counter, so the result writes of the whole GPU bunch into the windows and the packet
     reads run alone between them: HBM turns between reading and writing far less often (floor
     kernel, tools/ubench/phase.hip: 0.855 -> 0.773 ms for 64M packets).
-    Slots: slot k = group & K'-1 of the wave's last superblocks; with wphase bit 31 (wide, the
+    Slots: slot k = group & K'-1 of the wave's last superblocks; with wphase WPHASE_WIDE (wide, the
     96-VGPR kernel) a wave's superblocks alternate between slots 0-7 and 8-15 (s98 bit 31 = the
     half of S_PREVG's superblock), so 16 groups fit (0.770 -> 0.753 ms, tools/ubench/phase2.hip).
     An unwritten slot of S_PREVG's half belongs to its superblock (index <= S_PREVG's) or to the
@@ -2465,14 +2566,15 @@ def store_phased(tag, final):
               "s_and_b32 %s, %s, 8" % (s(S_T1), s(S_T1)),
               "s_cmp_eq_u32 %s, 0" % s(S_T0),
               "s_cbranch_scc0 .Lph_nf_%s" % tag,
-              "s_bitcmp1_b32 %s, 31" % s(S_WPHASE),
+              "s_bitcmp1_b32 %s, %d" % (s(S_WPHASE), WPHASE_WIDE),
               "s_cbranch_scc0 .Lph_nf_%s" % tag,
               "s_xor_b32 %s, %s, 8" % (s(S_T1), s(S_T1)),           # (a new superblock's half)
               ".Lph_nf_%s:" % tag,
               "s_or_b32 %s, %s, %s" % (s(S_T0), s(S_T0), s(S_T1)),
               "s_bitcmp1_b32 %s, %s" % (P, s(S_T0)),
               "s_cbranch_scc1 .Lph_write_%s" % tag,
-              "s_and_b32 %s, %s, 0x1f0000" % (s(S_T1), s(S_WPHASE)),   # width, offset 0
+              # (width, offset 0)
+              "s_and_b32 %s, %s, 0x%x" % (s(S_T1), s(S_WPHASE), 0x1f << WPHASE_PERIOD_SHIFT),
               "s_and_b32 %s, %s, 0xffff" % (s(S_T2), s(S_WPHASE)),
               "s_bfe_u32 %s, %s, %s" % (s(S_T0), s(S_CLOCK), s(S_T1)),
               "s_cmp_lt_u32 %s, %s" % (s(S_T0), s(S_T2)),
@@ -2483,7 +2585,7 @@ def store_phased(tag, final):
           "s_andn2_b32 %s, %s, %s" % (s(S_T1), s(S_PREVG), s(S_KMASK)),  # cur: S_PREVG's superblock
           "s_add_u32 %s, %s, %s" % (s(S_T2), s(S_GSTRIDE), s(S_KMASK)),  # superblock stride
           "s_sub_u32 %s, %s, %s" % (s(S_T0), s(S_T1), s(S_T2)),         # prev: the one before
-          "s_bitcmp1_b32 %s, 31" % s(S_WPHASE),
+          "s_bitcmp1_b32 %s, %d" % (s(S_WPHASE), WPHASE_WIDE),
           "s_cselect_b32 %s, %s, 0" % (s(S_T2), s(S_T2)),
           "s_sub_u32 %s, %s, %s" % (s(S_T2), s(S_T0), s(S_T2)),         # back
           "s_and_b32 %s, %s, %s" % (s(S_T3), s(S_PREVG), s(S_KMASK)),   # S_PREVG's slot index
@@ -2602,7 +2704,7 @@ def next_group(dst):
 
 
 def common_group_code():
-    """Shared by all kernels (s7 bit 0: staged 64-B packets; bit 1: compiled program)."""
+    """Shared by all kernels (MODE_STAGED: staged 64-B packets; MODE_JIT: compiled program)."""
     L = [".Lcb:",
          "ebpf_cb:",
          ".Lprologue:"]
@@ -2671,7 +2773,7 @@ def common_group_code():
           "s_lshl_b32 %s, s2, 2" % s(S_GROUP),
           "s_add_u32 %s, %s, %s" % (s(S_GROUP), s(S_GROUP), s(S_WAVE)),
           # K' = superblock size of this launch (total_waves bits 28..29 = log2 K')
-          "s_lshr_b32 %s, %s, 28" % (s(S_T1), s(S_GSTRIDE)),
+          "s_lshr_b32 %s, %s, %d" % (s(S_T1), s(S_GSTRIDE), WAVES_SB_SHIFT),
           "s_and_b32 %s, %s, 0xffff" % (s(S_GSTRIDE), s(S_GSTRIDE)),
           "s_lshl_b32 %s, 1, %s" % (s(S_KMASK), s(S_T1)),
           "s_sub_u32 %s, %s, 1" % (s(S_KMASK), s(S_KMASK)),
@@ -2683,15 +2785,15 @@ def common_group_code():
           # this wave's packet buffer (staged kernel); first group's prefetch
           "s_lshl_b32 %s, %s, 12" % (s(S_T0), s(S_WAVE)),
           "s_add_u32 %s, %s, %s" % (s(S_PKTLDS), s(S_PKTLDS), s(S_T0)),
-          "s_bitcmp1_b32 s7, 0",
+          mode_test(MODE_STAGED),
           "s_cbranch_scc0 .Lgroup_check",
           "s_mov_b32 %s, %s" % (s(S_T0), s(S_GROUP))] + call(".Lr_prefetch") + [
           "s_branch .Lgroup_check"]
     L += [".Lgroup_done:"]
     L += slot_commit() + next_group(S_T0) + [
-          # keep mode (s7 bits 14 and 0: staged kernels): the next group's DMA, now that the
+          # keep mode (MODE_KEEP and MODE_STAGED: staged kernels): the next group's DMA, now that the
           # program is done with the packet buffer
-          "s_and_b32 %s, s7, 0x4001" % s(S_BYTES),
+          "s_and_b32 %s, %s, 0x%x" % (s(S_BYTES), s(S_MODE), 1 << MODE_KEEP | 1 << MODE_STAGED),
           "s_cmp_eq_u32 %s, 0x4001" % s(S_BYTES),
           "s_cbranch_scc0 .Lgd_nokeep"] + call(".Lr_prefetch") + [
           ".Lgd_nokeep:",
@@ -2707,10 +2809,10 @@ def common_group_code():
            "s_cbranch_scc1 .Lgc_noclock",
            "s_memrealtime s[%d:%d]" % (S_CLOCK, S_CLOCK + 1),
            ".Lgc_noclock:"] if phased() else []) + lane_index(H[0]) + [
-          "v_lshl_add_u32 v%d, %s, 6, %s" % (H[3], s(S_GROUP), v(H[0])),      # packet index
-          "v_cmp_gt_u32_e64 %s, %s, v%d" % (sp(S_ALIVE), s(S_COUNT), H[3]),
+          "v_lshl_add_u32 v%d, %s, 6, %s" % (V_GIDX, s(S_GROUP), v(H[0])),      # packet index
+          "v_cmp_gt_u32_e64 %s, %s, v%d" % (sp(S_ALIVE), s(S_COUNT), V_GIDX),
           ] + [
-          "s_bitcmp1_b32 s7, 0",
+          mode_test(MODE_STAGED),
           "s_cbranch_scc0 .Lgs_general",
           # staged: this group's packets are (or are being) DMA'd into the packet buffer
           "s_waitcnt vmcnt(0)",
@@ -2724,12 +2826,12 @@ def common_group_code():
                                                           v(H[1]), 256 * q))
     # next group's DMA: a full group (the common case) inline, with exec = all lanes and the
     # instruction offset stepping both the global and the LDS address (M0 set once); a partial
-    # group through the masking routine.  (Keep mode, s7 bit 14: none here; .Lgroup_done
+    # group through the masking routine.  (Keep mode, MODE_KEEP: none here; .Lgroup_done
     # issues it once the program is done with the buffer)
     # (keep mode: the group's packets rewritten transposed for the program's loads at run-time
     # offsets, lds_pkt_dwords, once every lane's staging read has returned)
     L += ["s_waitcnt lgkmcnt(0)",
-          "s_bitcmp1_b32 s7, 14",
+          mode_test(MODE_KEEP),
           "s_cbranch_scc0 .Lgs_pf_dma",
           "v_lshrrev_b32 %s, 2, v%d" % (v(H[1]), V_L16),
           "v_add_u32 %s, %s, %s" % (v(H[1]), s(S_PKTLDS), v(H[1]))] + lds_pkt_dwords(v(H[1])) + [
@@ -2751,21 +2853,21 @@ def common_group_code():
           ".Lgs_pf_slow:"] + call(".Lr_prefetch") + [
           ".Lgs_pf_done:",
           # a compiled program computes the packet address itself if it needs it
-          "s_bitcmp1_b32 s7, 1",
+          mode_test(MODE_JIT),
           "s_cbranch_scc1 .Lgs_init",
           "s_mov_b64 exec, %s" % sp(S_ALIVE),
           "v_mov_b32 %s, 64" % v(H[1]),
-          "v_mad_u64_u32 v[%d:%d], %s, v%d, %s, %s" % (V_PKT, V_PKT + 1, sp(S_JUNK), H[3],
+          "v_mad_u64_u32 v[%d:%d], %s, v%d, %s, %s" % (V_PKT, V_PKT + 1, sp(S_JUNK), V_GIDX,
                                                        v(H[1]), sp(S_DATA)),
           "v_mov_b32 v%d, 64" % V_LEN,
           "s_branch .Lgs_init",
           ".Lgs_general:",
-          "s_mov_b64 exec, %s" % sp(S_ALIVE)] + pkt_setup(H[3], "g") + [
+          "s_mov_b64 exec, %s" % sp(S_ALIVE)] + pkt_setup(V_GIDX, "g") + [
           ".Lgs_init:"] + store_prev_results("g", False) + [
           "s_mov_b32 %s, %s" % (s(S_PREVG), s(S_GROUP))] + ([] if STAGED_IMAGE else [
           # V_IDX: this group's packet indices (after the previous group's store read them)
           "s_mov_b64 exec, -1",
-          "v_mov_b32 v%d, v%d" % (V_IDX, H[3])]) + [
+          "v_mov_b32 v%d, v%d" % (V_IDX, V_GIDX)]) + [
           "s_mov_b64 exec, %s" % sp(S_ALIVE),
           # fault code 0 for the whole group up front (a faulting lane overwrites its byte)
           "s_cmp_eq_u64 %s, 0" % sp(S_FAULTS),
@@ -2774,10 +2876,10 @@ def common_group_code():
           "v_mov_b32 %s, 0" % v(R[8]),
           "global_store_byte %s, %s, %s" % (v(R[9]), v(R[8]), sp(S_FAULTS)),
           ".Lgs_nofz:",
-          # a compiled program (s7 bit 1) starts at the head of its code area and sets up the
+          # a compiled program (MODE_JIT) starts at the head of its code area and sets up the
           # registers it reads itself (packet address, r1, r10, zeroes: asm_cc.cpp prologue)
-          "s_bitcmp1_b32 s7, 1",
-          "s_cbranch_scc0 .Lgs_interp"] + goto("ebpf_jit_area+16") + [
+          mode_test(MODE_JIT),
+          "s_cbranch_scc0 .Lgs_interp"] + goto("ebpf_jit_area+%d" % JIT_ENTRY_OFF) + [
           ".Lgs_interp:"]
     # r0, r2..r9 start at zero
     for r in range(0, 20, 2):
@@ -2867,8 +2969,8 @@ def common_group_code():
           "v_add_u32 %s, %s, %s" % (v(H[1]), s(S_T0), v(H[0])),       # bin
           "v_lshlrev_b32 %s, 2, %s" % (v(H[2]), v(H[1])),
           "ds_read_b32 %s, %s" % (v(H[3]), v(H[2])),
-          "s_load_dwordx2 %s, s[0:1], 0x68" % sp(S_REC),               # dp_launch.hist_rows
-          "s_load_dwordx4 s[68:71], s[0:1], 0x70",     # hist_user, hist_flags, nwg
+          "s_load_dwordx2 %s, %s" % (sp(S_REC), karg("hist_rows")),
+          "s_load_dwordx4 s[68:71], %s" % karg("hist_user", "hist_flags", "nwg"),
           "s_waitcnt lgkmcnt(0)",
           "s_cmp_eq_u64 %s, 0" % sp(S_REC),
           "s_cbranch_scc1 .Lfin_atomic",
@@ -2944,7 +3046,7 @@ def common_group_code():
     L += ["s_waitcnt vmcnt(0)"]
     for r in range(1, HIST_REPLICAS):
         L += ["v_lshl_add_u64 v[0:1], v[%d:%d], 0, v[0:1]" % (2 * r, 2 * r + 1)]
-    L += ["s_bitcmp1_b32 s70, 0",                   # hist_flags bit 0: store (overwrite)
+    L += ["s_bitcmp1_b32 s70, %d" % HIST_STORE,                   # hist_flags: store (overwrite)
           "s_cbranch_scc0 .Lfin_add",
           "global_store_dwordx2 %s, v[0:1], s[68:69]" % v(R[0]),
           "s_branch .Lfin_faults",
@@ -2959,7 +3061,7 @@ def common_group_code():
           "v_mov_b32 v17, %d" % (HIST_TICKET_OFF + 64 * HIST_REPLICAS),   # the top ticket
           "global_atomic_swap v18, v17, v24, %s sc0" % sp(S_REC),
           "s_waitcnt vmcnt(0)",
-          "s_bitcmp1_b32 s70, 0",
+          "s_bitcmp1_b32 s70, %d" % HIST_STORE,
           "s_cbranch_scc0 .Lfin_fadd",
           "global_store_dwordx2 v16, v[2:3], s[68:69]",
           "s_branch .Lfin_end",
@@ -2984,8 +3086,8 @@ def link_kernel():
     """ebpf_asm_link(dp_entry *e, uint32_t n): e[i].handler (= handler id) -> absolute address."""
     return [".globl ebpf_asm_link", ".p2align 8", ".type ebpf_asm_link,@function",
             "ebpf_asm_link:",
-            "s_load_dwordx2 s[4:5], s[0:1], 0x0",
-            "s_load_dword s6, s[0:1], 0x8",
+            "s_load_dwordx2 s[4:5], %s" % karg("entries", table=LINK_ARGS),
+            "s_load_dword s6, %s" % karg("count", table=LINK_ARGS),
             "s_getpc_b64 s[8:9]",
             ".Llink_base:",
             "s_add_u32 s10, s8, .Lhandler_table-.Llink_base",
@@ -3053,6 +3155,7 @@ def metadata(kernels):
 
 
 JIT_AREA_BYTES = 512 * 1024
+JIT_ENTRY_OFF = 16     # a compiled program starts here in the area (the bytes before: never executed)
 ENTRY_SGPR_RE = None
 
 
@@ -3120,17 +3223,72 @@ def jit_templates():
           "s_addc_u32 %s, %s, 0" % (s(S_JUNK + 1), s(S_CB + 1)),
           "s_setpc_b64 %s" % sp(S_JUNK),
           ".Ljt_jl_end:"]
-    # offsets from .Lcb, read by asm_jit.cpp (order = enum jt_index there)
-    names = [".Ljt_mov_s%d" % r for r in range(10, 16)] + [
-        ".Ljt_cs", ".Ljt_cs_br", ".Ljt_cs_vt", ".Ljt_cs_end",
-        ".Ljt_cl", ".Ljt_cl_lit", ".Ljt_cl_vt", ".Ljt_cl_end",
-        ".Ljt_br", ".Ljt_jl", ".Ljt_jl_end", ".Ljt_wait", ".Lr_exit_k", ".Lr_exit", ".Lr_fault",
-        ".Lr_hlookup", ".Lgroup_done",
-        ".Lr_schedule",
-        "ebpf_jit_area"]
-    L += [".p2align 2", "ebpf_jit_tmpl:"] + ["  .long %s-.Lcb" % n for n in names]
+    L += [".p2align 2", "ebpf_jit_tmpl:"] + ["  .long %s-.Lcb" % n for n in JT_LABELS]
     L += ["  .long %d" % JIT_AREA_BYTES]
     return L
+
+
+# ebpf_jit_tmpl: offsets from .Lcb of the glue above and of the routines compiled programs reach,
+# then the area's size.  asm_jit.cpp indexes it by AH_JT_<label without its .Ljt_ / .Lr_ / .L /
+# ebpf_ prefix, in capitals> (header_abi), so the order here is the only order there is.
+JT_LABELS = [".Ljt_mov_s%d" % r for r in range(10, 16)] + [
+    ".Ljt_cs", ".Ljt_cs_br", ".Ljt_cs_vt", ".Ljt_cs_end",
+    ".Ljt_cl", ".Ljt_cl_lit", ".Ljt_cl_vt", ".Ljt_cl_end",
+    ".Ljt_br", ".Ljt_jl", ".Ljt_jl_end", ".Ljt_wait", ".Lr_exit_k", ".Lr_exit", ".Lr_fault",
+    ".Lr_hlookup", ".Lgroup_done",
+    ".Lr_schedule",
+    "ebpf_jit_area"]
+
+
+def header_abi():
+    """The asm_handlers.h lines of the ABI section above (the same for every image)."""
+    out = ["// dp_launch fields the kernels load (byte offsets) and the kernarg size; "
+           "asm_runtime.cpp asserts them"]
+    out += ["#define AH_L_%s 0x%x" % (f.upper(), off) for f, (off, _) in LAUNCH.items()]
+    out += ["#define AH_KERNARG_BYTES %d" % KERNARG_BYTES,
+            "#define AH_LAUNCH_FIELDS(X) " + " ".join("X(%s, AH_L_%s)" % (f, f.upper()) for f in LAUNCH)]
+    out += ["#define AH_LINK_%s 0x%x" % (f.upper(), off) for f, (off, _) in LINK_ARGS.items()]
+    out += ["#define AH_LINK_KERNARG_BYTES %d" % LINK_KERNARG_BYTES]
+    out += ["#define AH_M_%s %d" % (f.upper(), off) for f, off in MAP_REC.items()]
+    out += ["#define AH_MAP_REC_BYTES %d" % MAP_REC_BYTES]
+    out += ["#define AH_E_%s %d" % (f.upper(), off) for f, off in ENTRY.items()]
+    out += ["#define AH_ENTRY_BYTES %d" % ENTRY_BYTES]
+    out += ["// registers the host compiler's encoders name (gen_interp.py register plan)"]
+    # (AH_S_OPND: s10..s15, the entry's operand words imm .. aux1; bit k of ah_reads = s(10 + k))
+    sregs = [("MODE", S_MODE), ("CB", S_CB), ("ENT", S_ENT), ("OPND", S_ENT + ENTRY["imm"] // 4),
+             ("SAVE", S_SAVE), ("DATA", S_DATA),
+             ("STKSTRIDE", S_STKSTRIDE), ("PKTLDS", S_PKTLDS), ("MASK", S_MASK), ("LINK", S_LINK),
+             ("CODE", S_CODE), ("BYTES", S_BYTES), ("SHARED", S_SHARED), ("JUNK", S_JUNK),
+             ("SHORT", S_SHORT)]
+    vregs = [("PKT0", PKT0), ("PKT", V_PKT), ("LEN", V_LEN), ("T", V_T), ("STK", V_STK),
+             ("L16", V_L16), ("RES", V_RES), ("GIDX", V_GIDX), ("HVAL", V_HVAL), ("SEL", V_SEL)]
+    vregs += [("H%d" % i, r) for i, r in enumerate(H)] + [("R%d" % i, r) for i, r in enumerate(R)]
+    out += ["#define AH_S_%s %d" % x for x in sregs] + ["#define AH_V_%s %d" % x for x in vregs]
+    out += ["// bits of the mode word s[AH_S_MODE]"]
+    out += ["#define AH_MODE_%s %d" % x for x in (
+        ("STAGED", MODE_STAGED), ("JIT", MODE_JIT), ("STRUCTURED", MODE_STRUCTURED),
+        ("HDRSTAGE", MODE_HDRSTAGE), ("OVERLAY", MODE_OVERLAY), ("KEEP", MODE_KEEP),
+        ("EXTENTS", MODE_EXTENTS))]
+    out += ["// dprog.h / ebpf_gpu.h values the kernels were generated with; asm_runtime.cpp asserts them"]
+    values = (
+        ("DP_VF_OVERLAY", 1 << VF_OVERLAY), ("DP_VF_VSTORE", 1 << VF_VSTORE),
+        ("DP_VF_EXTENTS", 1 << VF_EXTENTS), ("DP_VF_KEEP", 1 << VF_KEEP), ("DP_VF_WCAP", 1 << VF_WCAP),
+        ("DP_VF_ENTRIES_SHIFT", VF_ENTRIES_SHIFT), ("DP_VF_ENTRIES_MAX", (1 << VF_ENTRIES_BITS) - 1),
+        ("DP_PKTLDS_HDRSTAGE", 1 << PKTLDS_HDRSTAGE), ("DP_PKTLDS_HDRKEEP", 1 << PKTLDS_HDRKEEP),
+        ("DP_WAVES_SB_SHIFT", WAVES_SB_SHIFT), ("DP_HIST_STORE", 1 << HIST_STORE),
+        ("DP_WPHASE_PERIOD_SHIFT", WPHASE_PERIOD_SHIFT), ("DP_WPHASE_WIDE", 1 << WPHASE_WIDE),
+        ("DP_LOOP_BUDGET", LOOP_BUDGET), ("DP_OVL_COUNT", OVL_COUNT), ("DP_OVL_SCRATCH", VST_SCRATCH),
+        ("DP_WCOUNT", WCOUNT), ("DP_OVL_ENTRIES", OVL_ENTRIES), ("DP_WRITES_MAX", WRITES_MAX),
+        ("EBPF_FAULT_WRITES", FAULT_WRITES), ("DP_HIST_REPLICAS", HIST_REPLICAS),
+        ("DP_HIST_REPLICA_BYTES", HIST_REPLICA_BYTES), ("DP_HIST_TICKET_OFF", HIST_TICKET_OFF),
+        ("DP_HIST_PARTIAL_BYTES", HIST_TICKET_OFF + 64 * (HIST_REPLICAS + 1)))
+    out += ["#define AH_%s %du" % x for x in values]
+    out += ["#define AH_SHARED_VALUES(X) " + " ".join("X(%s)" % n for n, _ in values)]
+    out += ["// ebpf_jit_tmpl's entries, in the table's order"]
+    jt = [re.sub(r"^(\.Ljt_|\.Lr_|\.L|ebpf_)", "", n).upper() for n in JT_LABELS] + ["AREA_BYTES"]
+    out += ["enum {"] + ["\tAH_JT_%s," % n for n in jt] + ["\tAH_JT_COUNT", "};"]
+    out += ["#define AH_JIT_ENTRY_OFF %d  // a compiled program's start block in ebpf_jit_area" % JIT_ENTRY_OFF]
+    return out
 
 
 # The staged image the assembly interpreter (variant 2) launches from (m3): one result group per
@@ -3245,6 +3403,7 @@ def generate(out_s, staged_image):
     header.append("static const uint8_t ah_fam[AH_COUNT] = {%s};" % ",".join(map(str, fam_of)))
     header.append("static const uint8_t ah_dst[AH_COUNT] = {%s};" % ",".join(map(str, dst_of)))
     header.append("static const uint8_t ah_src[AH_COUNT] = {%s};" % ",".join(map(str, src_of)))
+    header += header_abi()
     header.append("#define AH_JIT_AREA_BYTES %d" % JIT_AREA_BYTES)
     header.append("#define AH_S_JOIN %d  // structured programs: taken-lane masks s[74:75]..  (staged image)" % S_JOIN)
     header.append("#define AH_JOIN_LEVELS %d" % JOIN_LEVELS)

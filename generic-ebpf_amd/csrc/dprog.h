@@ -60,12 +60,32 @@ enum dp_kind : uint16_t {
 	// here: the lane's overlay is emptied and its write count zeroed (DP_OVL_COUNT, DP_WCOUNT = 0)
 	DK_OVLINIT = 0x113,
 };
-#define DP_VF_EXTENTS 4u // dp_launch.vflags: offsets are (start, end) pairs
+// dp_launch.vflags.  (The assembly kernels test these, and the other dp_launch sub-fields named
+// below, by bit number: gen_interp.py keeps a copy of every value, and asm_runtime.cpp asserts
+// the copies against this header.)
+#define DP_VF_OVERLAY 1u // the program reads its own stores into map values (DP_OVL_* below)
+#define DP_VF_VSTORE 2u  // the program has value-store sites
+#define DP_VF_EXTENTS 4u // offsets are (start, end) pairs (EBPF_BATCH_EXTENTS)
 // dp_launch.vflags: the assembly interpreter's staged kernel keeps each group's packets in the
 // wave's LDS packet buffer until the group ends (keep mode: LDXPKTV reads them there)
 #define DP_VF_KEEP 8u
 // dp_launch.vflags: count each packet's logged writes and fault the one past DP_WRITES_MAX
 #define DP_VF_WCAP 16u
+// dp_launch.vflags bits 8..15: the overlay's entries per lane
+#define DP_VF_ENTRIES_SHIFT 8u
+#define DP_VF_ENTRIES_MAX 255u
+// dp_launch.lds_pkt_base, above the LDS offset (general assembly kernels): stage the packets'
+// first 64 bytes into registers; ... and keep them in the wave's LDS packet buffer too
+#define DP_PKTLDS_HDRSTAGE 0x80000000u
+#define DP_PKTLDS_HDRKEEP 0x40000000u
+// dp_launch.total_waves: log2 of the superblock size, above the wave count
+#define DP_WAVES_SB_SHIFT 28u
+// dp_launch.hist_flags: the last workgroup stores the reduced histogram (else adds it)
+#define DP_HIST_STORE 1u
+// dp_launch.wphase: window | log2(period) << DP_WPHASE_PERIOD_SHIFT; DP_WPHASE_WIDE = the wide
+// kernel (16 result slots)
+#define DP_WPHASE_PERIOD_SHIFT 16u
+#define DP_WPHASE_WIDE 0x80000000u
 #define DP_LOOP_BUDGET (1u << 20) // taken backward jumps a lane may make (standard semantics)
 #define DP_CLS_JMP32 6
 
@@ -156,15 +176,16 @@ struct dp_launch {
 	// assembly interpreter only:
 	uint32_t stack_stride;    // LDS bytes per lane stack slice (S' in asm_runtime.cpp)
 	uint32_t lds_stack_base;  // LDS byte offset of the first stack slice (after the histogram)
-	uint32_t total_waves;     // persistent grid: waves in the launch (group stride); bits
-	                          // 28..29: log2 of the superblock size (staged kernels)
+	uint32_t total_waves;     // persistent grid: waves in the launch (group stride); from
+	                          // DP_WAVES_SB_SHIFT up: log2 of the superblock size (staged kernels)
 	uint32_t lds_pkt_base;    // staged kernel: LDS byte offset of the per-wave packet buffers
+	                          // (| DP_PKTLDS_* in the general kernels)
 	uint32_t *hist_rows;      // assembly kernels: the launch's private verdict partials
 	                          // (DP_HIST_* layout below; hist points at it too, so faults count
 	                          // into replica 0's bin 256); NULL = per-bin atomics into hist
-	unsigned long long *hist_user; // the caller's histogram: the last workgroup stores (flags
-	                          // bit 0) or adds the reduced partials there
-	uint32_t hist_flags;      // bit 0: store instead of add (EBPF_BATCH_HIST_OVERWRITE)
+	unsigned long long *hist_user; // the caller's histogram: the last workgroup stores
+	                          // (DP_HIST_STORE) or adds the reduced partials there
+	uint32_t hist_flags;      // DP_HIST_STORE: store instead of add (EBPF_BATCH_HIST_OVERWRITE)
 	uint32_t nwg;             // workgroups in this launch (the ticket's arrival count)
 	// map writes (DK_CALL_UPDATE): the batch's log, u32 record count at +0, records from +64:
 	// {u64 packet index, u32 entry | map << 20, u32 key, value[value_size]}, upd_stride apart
@@ -172,19 +193,21 @@ struct dp_launch {
 	uint32_t upd_cap;         // records the log holds
 	uint32_t upd_stride;
 	uint64_t pkt_base;        // index of this launch's first packet in its batch
-	uint8_t *reserved0;       // (unused; keeps the offsets the assembly kernels load)
+	uint8_t *reserved0;       // (reservedN: unused; they keep the later members at the offsets the
+	                          // assembly kernels were generated with, which asm_runtime.cpp asserts
+	                          // member by member against asm_handlers.h AH_L_*)
 	uint32_t reserved1;
 	uint32_t reserved2;
 	// map writes: one bit per packet of the batch (index pkt_base + i, cleared by the host before
 	// the batch), set when the packet faults; the apply step skips a faulted packet's logged
 	// writes (a packet that faults leaves no write behind).  NULL for programs without map writes
 	uint32_t *upd_faulted;
-	const void *reserved3[2]; // (unused; keep vflags at the offset the assembly kernels load)
+	const void *reserved3[2];
 	uint32_t reserved4[3];
-	// stores into map values (ebpf_gpu.h "Stores into map values"): bit 0 = the program reads
-	// its own stores (an overlay of the words it stored, per lane: DP_OVL_* below); bit 1 = it
-	// has value-store sites; bit 2 (DP_VF_EXTENTS) = `offsets` holds (start, end) pairs
-	// (EBPF_BATCH_EXTENTS); bits 8..15 = the overlay's entries per lane
+	// DP_VF_* above.  Stores into map values (ebpf_gpu.h "Stores into map values"):
+	// DP_VF_OVERLAY = the program reads its own stores (an overlay of the words it stored, per
+	// lane: DP_OVL_* below), DP_VF_VSTORE = it has value-store sites, and from
+	// DP_VF_ENTRIES_SHIFT up the overlay's entries per lane
 	uint32_t vflags;
 	// staged kernels with result bursts: write phasing (gen_interp.py store_phased).  A wave keeps
 	// its finished groups' results in registers and writes them while the GPU's constant clock
@@ -202,9 +225,8 @@ struct dp_launch {
 	uint32_t reserved5;
 	uint8_t *ovl_spill;
 };
-static_assert(sizeof(dp_launch) == 232, "dp_launch layout is shared with the assembly kernels");
-static_assert(offsetof(dp_launch, vflags) == 0xcc, "gen_interp.py VFLAGS_OFF");
-static_assert(offsetof(dp_launch, wphase) == 0xd0, "gen_interp.py WPHASE_OFF");
+// (the layout is shared with the assembly kernels: asm_runtime.cpp asserts the size and the
+// offset of every member they load against the generator's table)
 
 // The lane's LDS stack slice, below the frame the program addresses: the loop count (+0), the
 // overlay's entry count (+4), an 8-byte scratch a store into a map value is redirected to (+8),

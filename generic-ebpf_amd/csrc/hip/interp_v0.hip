@@ -81,7 +81,7 @@ check(const regions &rg, const dp_launch &L, uint64_t a, uint32_t size, bool wri
 	return F_MEM;
 }
 
-// The packet's own stores into map values (dp_launch.vflags bit 0): whole 8-byte words of the
+// The packet's own stores into map values (dp_launch.vflags DP_VF_OVERLAY): whole 8-byte words of the
 // mirror as the packet sees them (dprog.h DP_OVL_*), newest last — in the lane's own DP_OVL_MAX
 // entries, or in its slice of dp_launch.ovl_spill (a loop-free program that reads back more)
 struct overlay {
@@ -240,7 +240,7 @@ value_store(const dp_launch &L, uint64_t gid, overlay &o, uint32_t &writes, int 
 		return F_WRITES;
 	// (a full overlay: only a program with loops that reads its counters back can fill it —
 	// ebpf_gpu.h, 32 words — the write that needs one more faults WRITES before it happens)
-	if ((L.vflags & 1) && !ovl_store(o, a, size, v))
+	if ((L.vflags & DP_VF_OVERLAY) && !ovl_store(o, a, size, v))
 		return F_WRITES;
 	if (atomic) {
 		uint8_t *d = reinterpret_cast<uint8_t *>(mp.dev_base) + dp_delta_off(mp.value_size, mp.max_entries) + off;

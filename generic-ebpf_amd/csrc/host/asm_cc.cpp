@@ -77,13 +77,31 @@ enum : uint32_t {
 enum : uint32_t { VC_I32 = 0xc0, VC_U32 = 0xc8, VC_I64 = 0xe0, VC_U64 = 0xe8 };
 enum { P_LT = 1, P_EQ = 2, P_LE = 3, P_GT = 4, P_NE = 5, P_GE = 6 };
 const uint32_t S_WAITCNT_LGKM0 = 0xbf8cc07fu;
-const int S_JUNK = 60; // s[60:61]: carry-out sink of v_mad_u64_u32 (gen_interp.py S_JUNK)
-const int S_BYTES = 57, S_CB = 4;              // gen_interp.py S_BYTES, S_CB
-const int T0 = 46, T1 = 47, T2 = 48, T3 = 49;  // handler temporaries (gen_interp.py H)
-const int PKT0 = 22;                           // staged packet dwords v22..v37
-const int V_STK = 42;                          // lane stack bottom (LDS byte address)
-const int V_RES = 44;                          // v[44:45]: r0 of retiring lanes
-const int V_SEL = 63;                          // v63 = 0x00010203 (byte reversal selector)
+// The kernels' registers this code names.  gen_interp.py assigns them and writes them into
+// asm_handlers.h; these are aliases, so a register that moves there moves here with it.  (eBPF
+// register rK in v[2K:2K+1] is the one convention both sides spell out: emitter::L / Hi.)
+const int S_MODE = AH_S_MODE;          // the mode word (AH_MODE_* bits)
+const int S_CB = AH_S_CB;              // s[4:5]: code base, routines are at S_CB + offset
+const int S_OPND = AH_S_OPND;          // s10..s15: the operand words a handler body reads
+const int S_SAVE = AH_S_SAVE;          // s[18:19]
+const int S_DATA = AH_S_DATA;          // s[24:25]: dp_launch.data
+const int S_STKSTRIDE = AH_S_STKSTRIDE;
+const int S_PKTLDS = AH_S_PKTLDS;      // LDS offset of the wave's packet buffer
+const int S_MASK = AH_S_MASK;          // s[48:49]: lanes argument of the fault routine, scratch
+const int S_LINK = AH_S_LINK;          // s[50:51]: routine return address
+const int S_CODE = AH_S_CODE;          // fault code argument
+const int S_BYTES = AH_S_BYTES;        // .Lr_exit_k: the verdict bin
+const int S_SHARED_HI = AH_S_SHARED + 1; // src_shared_base, high word
+const int S_JUNK = AH_S_JUNK;          // s[60:61]: scratch pair, carry-out sink of v_mad_u64_u32
+const int S_SHORT = AH_S_SHORT;        // s[74:75], general kernels: lanes with a packet below 64 B
+const int PKT0 = AH_V_PKT0;            // the 16 staged packet dwords
+const int V_PKT = AH_V_PKT;            // v[38:39]: packet address
+const int V_LEN = AH_V_LEN;            // packet length
+const int V_STK = AH_V_STK;            // lane stack bottom (LDS byte address)
+const int V_L16 = AH_V_L16;            // staged kernels: lane * 16
+const int V_RES = AH_V_RES;            // v[44:45]: r0 of retiring lanes
+const int V_SEL = AH_V_SEL;            // 0x00010203 (byte reversal selector)
+const int T0 = AH_V_H0, T1 = AH_V_H1, T2 = AH_V_H2, T3 = AH_V_H3; // handler temporaries
 
 struct opnd {
 	uint32_t code;
@@ -348,7 +366,7 @@ struct emitter {
 	// * every running lane at the same offset (a cursor advanced by constants: C3L's header
 	//   words): from the packet dwords v22..v37 the staging left in registers, indexed by the
 	//   offset's dword (s_set_gpr_idx_on, M0) and aligned by its low bits — no memory access;
-	// * otherwise, in keep mode (s7 bit 14: gpu_runtime.cpp sets it for staged launches of
+	// * otherwise, in keep mode (AH_MODE_KEEP: gpu_runtime.cpp sets it for staged launches of
 	//   programs with these loads), from the wave's transposed LDS packet buffer (gen_interp.py
 	//   lds_pkt_read) when every running lane's bytes lie in its 64;
 	// * else the interpreter's handler body h (generic load, faults), spliced in by the code
@@ -357,8 +375,8 @@ struct emitter {
 	// first: here r_sr is read directly and K folds into the bounds.)
 	void ldxpktv_staged(int d, int sr, int z, uint32_t K, int h)
 	{
-		const int V_PKT = 38, V_L16 = 43, S_PKTLDS = 47, S_U = 60, S_M = 48;
-		const int A = 50, B = 51, R0 = 52, R1 = 53, R2 = 54; // (gen_interp.py H[4], H[5], R[0..2])
+		const int S_U = S_JUNK, S_M = S_MASK;
+		const int A = AH_V_H4, B = AH_V_H5, R0 = AH_V_R0, R1 = AH_V_R1, R2 = AH_V_R2;
 		const uint32_t C = 64u - (uint32_t)z - K;            // last in-bounds offset T
 		use(sr);
 		auto sopc = [&](uint32_t op, uint32_t s0, uint32_t s1) {
@@ -401,7 +419,7 @@ struct emitter {
 			hi0(d);
 		const size_t done0 = fwd(BR);                                // (patched past the splice)
 		to(to_lds);
-		sopc(0x0d, 7, 128 + 14);                                     // s_bitcmp1_b32 s7, 14
+		sopc(0x0d, S_MODE, 128 + AH_MODE_KEEP);                      // s_bitcmp1_b32 s7, 14
 		const size_t slow2 = fwd(SCC0);                              // no keep mode: the handler
 		E.vopc(VC_U64 + P_GE, k32(C), T2);                           // vcc = T <= C
 		E.sop2(0x13, S_JUNK, opnd{SRC_EXEC}, opnd{SRC_VCC});        // s_andn2_b64: lanes out
@@ -445,15 +463,14 @@ struct emitter {
 	// an SGPR holding the 32-bit constant v for this body (s13, s14, s15)
 	uint32_t sconst(uint32_t v)
 	{
-		static const int regs[3] = {13, 14, 15};
-		for (int r : regs)
-			if ((blk.reads & (1u << (r - 10))) && blk.sval[r - 10] == v)
-				return (uint32_t)r;
-		for (int r : regs)
-			if (!(blk.reads & (1u << (r - 10)))) {
-				blk.reads |= (uint8_t)(1u << (r - 10));
-				blk.sval[r - 10] = v;
-				return (uint32_t)r;
+		for (int k = 3; k < 6; k++)
+			if ((blk.reads & (1u << k)) && blk.sval[k] == v)
+				return (uint32_t)(S_OPND + k);
+		for (int k = 3; k < 6; k++)
+			if (!(blk.reads & (1u << k))) {
+				blk.reads |= (uint8_t)(1u << k);
+				blk.sval[k] = v;
+				return (uint32_t)(S_OPND + k);
 			}
 		return UINT32_MAX; // never: no body needs four constants
 	}
@@ -463,7 +480,7 @@ struct emitter {
 		blk.reads |= 3;
 		blk.sval[0] = (uint32_t)v;
 		blk.sval[1] = (uint32_t)(v >> 32);
-		return 10;
+		return (uint32_t)S_OPND;
 	}
 	uint32_t c3(uint32_t v)
 	{
@@ -935,7 +952,6 @@ struct emitter {
 	// from memory; when none is running the load is the extract alone.
 	void ldxpkc_general(int d, int z, int off, uint32_t fault_off)
 	{
-		const int S_SHORT = 74, S_MASK = 48, S_CODE = 52, S_JUNK_ = 60, V_LEN = 40, V_PKT = 38;
 		static const uint32_t gop[4] = {0x10, 0x12, 0x14, 0x15};
 		const int zi = z == 1 ? 0 : z == 2 ? 1 : z == 4 ? 2 : 3;
 		auto patch = [&](size_t at) { // branch at byte `at` jumps to here
@@ -956,14 +972,14 @@ struct emitter {
 		E.sop2(0x0d, S_MASK, opnd{(uint32_t)S_SHORT}, opnd{SRC_EXEC});
 		const size_t to_end1 = blk.body.size();
 		E.w(0xbf840000u);                                                 // s_cbranch_scc0 end
-		E.sop1(0x01, S_JUNK_, opnd{SRC_EXEC});                           // s_mov_b64 s60, exec
+		E.sop1(0x01, S_JUNK, opnd{SRC_EXEC});                           // s_mov_b64 s60, exec
 		E.sop1(0x01, 126, opnd{(uint32_t)S_MASK});                       // exec = short lanes
 		E.w(0xdc008000u | (gop[zi] << 18) | (uint32_t)off);              // global_load_*
 		E.w((uint32_t)V_PKT | (0x7fu << 16) | ((uint32_t)L(d) << 24));
 		E.w(0xbf8c0f70u);                                                 // s_waitcnt vmcnt(0)
 		if (z < 8)
 			mov32(Hi(d), 0);
-		E.sop1(0x01, 126, opnd{(uint32_t)S_JUNK_});                      // exec back
+		E.sop1(0x01, 126, opnd{(uint32_t)S_JUNK});                      // exec back
 		const size_t to_end2 = blk.body.size();
 		E.w(0xbf820000u);                                                 // s_branch end
 		patch(to_fast);
@@ -1165,7 +1181,7 @@ struct emitter {
 			// of popcount(exec) to bin min(r0, 255); the exiting lanes leave the alive mask
 			// (lane 0's V_L16 = 0 addresses the bin through the instruction offset; the alive
 			// mask is not read again before the group ends in a structured program)
-			const int S_CODE = 52, S_SAVE = 18, R8 = 60, V_L16 = 43;
+			const int R8 = AH_V_R8;
 			const uint32_t bin = r0 < 255 ? (uint32_t)r0 : 255u;
 			E.sop1(0x0d, S_CODE, opnd{SRC_EXEC});                         // s_bcnt1_i32_b64
 			E.sop1(0x01, S_SAVE, opnd{SRC_EXEC});                         // s_mov_b64
@@ -1186,7 +1202,7 @@ struct emitter {
 	// the return and the uniform-verdict test)
 	void exit_inline()
 	{
-		const int R8 = 60, R9 = 61;
+		const int R8 = AH_V_R8, R9 = AH_V_R9;
 		use(0);
 		E.vop1(V1_MOV_B32, V_RES, vreg(0));
 		E.vop1(V1_MOV_B32, V_RES + 1, vreg(1));
@@ -1205,7 +1221,6 @@ struct emitter {
 	// call a routine that returns (structured programs): the link pair s[50:51]
 	void call_routine(uint32_t off, uint16_t reads)
 	{
-		const int S_LINK = 50;
 		used |= reads;
 		E.sop2(0x00, S_LINK, opnd{(uint32_t)S_CB}, opnd{SRC_LIT, off});     // s_add_u32
 		E.sop2(0x04, S_LINK + 1, opnd{(uint32_t)S_CB + 1}, opnd{128});     // s_addc_u32
@@ -1222,7 +1237,6 @@ struct emitter {
 	void ldx_hoisted(int d, int z, uint32_t off, int tmp, uint32_t later, uint32_t fault_off,
 			 bool runmask)
 	{
-		const int S_MASK = 48, S_CODE = 52, V_LEN = 40, S_JUNK_ = 60, V_PKT = 38;
 		size_t br = 0, from = 0;
 		if (runmask) {
 			E.sop2(0x13, S_MASK, opnd{SRC_EXEC}, opnd{(uint32_t)AH_S_RUNMASK}); // s_andn2_b64
@@ -1240,12 +1254,12 @@ struct emitter {
 			const int zi = z == 1 ? 0 : z == 2 ? 1 : z == 4 ? 2 : 3;
 			E.sop2(0x13, S_MASK, opnd{SRC_EXEC}, opnd{(uint32_t)AH_S_RUNMASK}); // in bounds, unmasked
 			E.w(0xbf840000u | 6u);                                           // s_cbranch_scc0 +6
-			E.sop1(0x01, S_JUNK_, opnd{SRC_EXEC});                           // s_mov_b64 s60, exec
+			E.sop1(0x01, S_JUNK, opnd{SRC_EXEC});                           // s_mov_b64 s60, exec
 			E.sop1(0x01, 126, opnd{(uint32_t)S_MASK});                       // s_mov_b64 exec, s48
 			E.w(0xdc008000u | (gop[zi] << 18) | off);                        // global_load_* tmp
 			E.w((uint32_t)V_PKT | (0x7fu << 16) | ((uint32_t)tmp << 24));
 			E.w(0xbf8c0f70u);                                                // s_waitcnt vmcnt(0)
-			E.sop1(0x01, 126, opnd{(uint32_t)S_JUNK_});                      // s_mov_b64 exec, s60
+			E.sop1(0x01, 126, opnd{(uint32_t)S_JUNK});                      // s_mov_b64 exec, s60
 			const uint32_t skip = (uint32_t)((E.b.size() - from) / 4);
 			E.b[br] = (uint8_t)skip;
 			E.b[br + 1] = (uint8_t)(skip >> 8);
@@ -1263,7 +1277,6 @@ struct emitter {
 	// FAULT entry (structured): fault every running lane with `code`
 	void fault(uint32_t code, uint32_t fault_off)
 	{
-		const int S_MASK = 48, S_CODE = 52;
 		E.sop1(0x00, S_CODE, k32(code));            // s_mov_b32 s52, code
 		E.sop1(0x01, S_MASK, opnd{SRC_EXEC});       // s_mov_b64 s[48:49], exec
 		call_routine(fault_off, 0);
@@ -1584,18 +1597,17 @@ cc_prologue(int mode, uint16_t live, bool needs_pkt, bool structured, std::vecto
 {
 	enc P{out};
 	if (structured)
-		P.sop2(0x0e, 7, opnd{7}, opnd{128 + 4}); // s_or_b32 s7, s7, 4
-	const int V_PKT = 38, V_LEN = 40, H1 = 47, H3 = 49, S_DATA = 24;
+		P.sop2(0x0e, S_MODE, opnd{(uint32_t)S_MODE},
+		       opnd{128 + (1u << AH_MODE_STRUCTURED)}); // s_or_b32 s7, s7, 4
 	if (mode == 1 && (needs_pkt || (live & (1u << 1)))) {
-		// staged kernel: packet address = data + index * 64 (index in v49, gen_interp.py H[3])
-		P.vop1(V1_MOV_B32, H1, opnd{128 + 64});
-		P.vop3(V3_MAD_U64_U32, V_PKT, VGPR0 + H3, VGPR0 + H1, S_DATA, S_JUNK);
+		// staged kernel: packet address = data + index * 64 (the kernel leaves the index in V_GIDX)
+		P.vop1(V1_MOV_B32, T1, opnd{128 + 64});
+		P.vop3(V3_MAD_U64_U32, V_PKT, VGPR0 + AH_V_GIDX, VGPR0 + T1, S_DATA, S_JUNK);
 		P.vop1(V1_MOV_B32, V_LEN, opnd{128 + 64});
 	}
 	if (live & (1u << 1))
 		P.vop1(V1_MOV_B64, 2, vreg(V_PKT));
 	if (live & (1u << 10)) {
-		const int S_STKSTRIDE = 42, S_SHARED_HI = 59;
 		P.vop2(V2_ADD_U32, 20, opnd{(uint32_t)S_STKSTRIDE}, V_STK);
 		P.vop1(V1_MOV_B32, 21, opnd{(uint32_t)S_SHARED_HI});
 	}
@@ -1739,8 +1751,8 @@ cc_compile(const dprog_host &xl, const std::vector<dp_entry> &low, const std::ve
 			const int fam = ah_fam[h], d = ah_dst[h], s = ah_src[h];
 			const uint64_t K = low[e].imm;
 			uint32_t aux0, aux1;
-			memcpy(&aux0, reinterpret_cast<const uint8_t *>(&low[e]) + 24, 4);
-			memcpy(&aux1, reinterpret_cast<const uint8_t *>(&low[e]) + 28, 4);
+			memcpy(&aux0, reinterpret_cast<const uint8_t *>(&low[e]) + AH_E_AUX0, 4);
+			memcpy(&aux1, reinterpret_cast<const uint8_t *>(&low[e]) + AH_E_AUX1, 4);
 			f.nofwd = (off & 4) != 0;
 			const facts before = f;
 			emitter em(blk, f, maps);
@@ -1749,32 +1761,31 @@ cc_compile(const dprog_host &xl, const std::vector<dp_entry> &low, const std::ve
 			// issue packet load x into its ring slot, for the lanes whose packet holds it
 			// (masked: exec is already the lanes to load for, the run head's batch)
 			auto issue = [&](enc &Hq, uint32_t x, bool masked = false) {
-				const int S_JUNK_ = 60, V_LEN = 40, V_PKT = 38;
 				const int fx = ah_fam[(uint32_t)low[x].handler];
 				const int z = 1 << (fx - AHF_LDXPKTG1);
 				const uint32_t K32 = (uint32_t)low[x].imm;
 				static const uint32_t gop[4] = {0x10, 0x12, 0x14, 0x15};
 				if (masked) {
 				} else if (runmask) {
-					Hq.sop1(0x20, S_JUNK_, opnd{(uint32_t)AH_S_RUNMASK}); // s_and_saveexec_b64
+					Hq.sop1(0x20, S_JUNK, opnd{(uint32_t)AH_S_RUNMASK}); // s_and_saveexec_b64
 				} else {
 					Hq.vopc(VC_U32 + P_LE, k32(K32 + (uint32_t)z), V_LEN); // vcc = off+z <= len
-					Hq.sop1(0x20, S_JUNK_, opnd{SRC_VCC});                  // s_and_saveexec_b64
+					Hq.sop1(0x20, S_JUNK, opnd{SRC_VCC});                  // s_and_saveexec_b64
 				}
 				Hq.w(0xdc008000u | (gop[fx - AHF_LDXPKTG1] << 18) | K32);      // global_load_*
 				Hq.w((uint32_t)V_PKT | (0x7fu << 16) | ((uint32_t)hoist_tmp[x] << 24));
 				if (!masked)
-					Hq.sop1(0x01, 126, opnd{(uint32_t)S_JUNK_});       // s_mov_b64 exec
+					Hq.sop1(0x01, 126, opnd{(uint32_t)S_JUNK});       // s_mov_b64 exec
 			};
 			if (!hoist_at[e].empty()) {
 				enc Hq{blk.hoist};
 				if (runmask) { // s[76:77] = the running lanes whose packet holds every load of the run
-					Hq.vopc(VC_U32 + P_LE, k32(run_ext[e]), 40); // vcc = ext <= len (v40)
+					Hq.vopc(VC_U32 + P_LE, k32(run_ext[e]), V_LEN); // vcc = ext <= len (v40)
 					Hq.sop1(0x01, AH_S_RUNMASK, opnd{SRC_VCC});    // s_mov_b64
-					Hq.sop1(0x20, 60, opnd{SRC_VCC});            // s_and_saveexec_b64 s[60:61]
+					Hq.sop1(0x20, S_JUNK, opnd{SRC_VCC});        // s_and_saveexec_b64 s[60:61]
 					for (uint32_t x : hoist_at[e])
 						issue(Hq, x, true);
-					Hq.sop1(0x01, 126, opnd{60u});               // s_mov_b64 exec, s[60:61]
+					Hq.sop1(0x01, 126, opnd{(uint32_t)S_JUNK});  // s_mov_b64 exec, s[60:61]
 				} else {
 					for (uint32_t x : hoist_at[e])
 						issue(Hq, x);
@@ -1913,10 +1924,10 @@ cc_compile(const dprog_host &xl, const std::vector<dp_entry> &low, const std::ve
 			case AHF_HLOOKUP: {
 				// (an inline jhash + home-slot probe, round 3, measured 3% slower than the
 				// generic routine on C4H and was retired in round 5)
-				const int mi = (int)(aux0 / 32);
+				const int mi = (int)(aux0 / sizeof(dp_map));
 				ok = false;
 				// the generic routine, whose probe of a key of <= 8 bytes also loads the
-				// slot's first 8 value bytes (v[50:51], gen_interp.py hlookup_routine): they
+				// slot's first 8 value bytes (AH_V_HVAL, the kernels' .Lr_hlookup): they
 				// are kept in a register D dead from here on, so that loads through the
 				// result (LDXHV) become register extracts (one memory round trip less)
 				if (!ok && final_pass && mi < (int)table.size() && (table[mi].flags & DP_MAP_HASH) &&
@@ -1944,7 +1955,7 @@ cc_compile(const dprog_host &xl, const std::vector<dp_entry> &low, const std::ve
 						blk.sval[4] = aux0;
 						em.use(2);
 						em.call_routine(rt.hlookup, 0);
-						em.E.vop1(V1_MOV_B64, 2 * D, vreg(50));
+						em.E.vop1(V1_MOV_B64, 2 * D, vreg(AH_V_HVAL));
 						f.def(0, rf());
 						// (D's value facts stay: the liveness that picked D was computed with
 						// them, so a compare they decided must stay decided — dropping them
@@ -2106,7 +2117,7 @@ cc_compile(const dprog_host &xl, const std::vector<dp_entry> &low, const std::ve
 				cc_prologue(mode, live_start, needs_pkt, structured, out[xl.start].prologue);
 				if (uses_short_mask) { // s[74:75] = lanes whose packet is shorter than 64 B
 					enc P{out[xl.start].prologue};
-					P.vop3(VC_U32 + P_GT, 74, 128 + 64, VGPR0 + 40, 0);
+					P.vop3(VC_U32 + P_GT, S_SHORT, 128 + 64, VGPR0 + V_LEN, 0);
 				}
 			}
 			break;

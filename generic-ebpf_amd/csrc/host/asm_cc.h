@@ -53,6 +53,6 @@ void cc_compile(const dprog_host &xl, const std::vector<dp_entry> &low, const st
 // The group set-up a compiled program does itself (the kernel jumps straight to it): the packet
 // address (staged mode), r1 = packet, r10 = stack top, zeroes for r0, r2..r9 — the registers in
 // `live` (bit r), the packet address also if `needs_pkt` (generic memory routines read it).
-// structured: also mark the wave's group as structured (s7 bit 2, read by the exit and fault
+// structured: also mark the wave's group as structured (AH_MODE_STRUCTURED, read by the exit and fault
 // routines).
 void cc_prologue(int mode, uint16_t live, bool needs_pkt, bool structured, std::vector<uint8_t> &out);

@@ -12,7 +12,11 @@
 // check, lookup, schedule) relative to .Lcb, whose offset is the same in every copy, so the
 // bytes need no relocation.  Divergence works as in the interpreter: lanes that take a branch
 // the rest of the wave does not are parked with v41 = the code offset of their block, and the
-// scheduler resumes them by jumping to .Lcb + v41 (s7 bit 1 selects that mode).
+// scheduler resumes them by jumping to .Lcb + v41 (AH_MODE_JIT selects that mode).
+//
+// The glue templates and routines are found through the image's ebpf_jit_tmpl table, indexed by
+// AH_JT_* (asm_handlers.h, generated with the table); registers are the generator's AH_S_* /
+// AH_V_*.
 //
 // The state graph is a tree, so every block is placed exactly once and each straight-line run
 // falls through; only taken branches (and shared fault entries) need jumps.
@@ -28,22 +32,21 @@ int asm_lower(const dprog_host &xl, int mode, const std::vector<dp_map> &table,
 
 namespace {
 
-// Order of ebpf_jit_tmpl in gen_interp.py.
-enum jt_index {
-	JT_MOV_S10 = 0, // .. JT_MOV_S10 + 5
-	JT_CS = 6, JT_CS_BR, JT_CS_VT, JT_CS_END,
-	JT_CL, JT_CL_LIT, JT_CL_VT, JT_CL_END,
-	JT_BR, JT_JL, JT_JL_END, JT_WAIT, JT_EXITK, JT_EXIT, JT_FAULT, JT_HLOOKUP, JT_GDONE,
-	JT_SCHED, JT_AREA, JT_AREA_BYTES,
-	JT_COUNT
-};
+// the operand moves are indexed AH_JT_MOV_S10 + r
+static_assert(AH_S_OPND == 10 && AH_JT_MOV_S11 == AH_JT_MOV_S10 + 1 && AH_JT_MOV_S12 == AH_JT_MOV_S10 + 2 &&
+		      AH_JT_MOV_S13 == AH_JT_MOV_S10 + 3 && AH_JT_MOV_S14 == AH_JT_MOV_S10 + 4 &&
+		      AH_JT_MOV_S15 == AH_JT_MOV_S10 + 5,
+	      "the s_mov templates of the operand registers s10..s15 are consecutive");
+
+// SOP1 / SOP2 / VOP1 words of the glue encoded here (exec = 126, vcc = 106, literal = 255)
+constexpr uint32_t S_JUNK = AH_S_JUNK, S_CB = AH_S_CB, S_MASK = AH_S_MASK, S_SAVE = AH_S_SAVE;
 
 struct jit_image {
 	bool ok = false;
 	std::string why;
 	size_t cb = 0;                          // file offset of .Lcb
 	std::vector<uint32_t> body_off, body_len; // per handler id, body offset from .Lcb, length
-	uint32_t t[JT_COUNT] = {};
+	uint32_t t[AH_JT_COUNT] = {};
 };
 
 bool
@@ -103,7 +106,7 @@ image_info(int mode)
 		I.cb = off[0];
 		const unsigned char *meta = img + off[1];
 		const unsigned char *tm = img + off[2];
-		if (off[1] + 8ull * AH_COUNT > len || off[2] + 4ull * JT_COUNT > len) {
+		if (off[1] + 8ull * AH_COUNT > len || off[2] + 4ull * AH_JT_COUNT > len) {
 			I.why = "compiled-program tables out of range";
 			return;
 		}
@@ -118,7 +121,7 @@ image_info(int mode)
 			}
 		}
 		memcpy(I.t, tm, sizeof(I.t));
-		if (I.t[JT_AREA_BYTES] != AH_JIT_AREA_BYTES || I.cb + I.t[JT_AREA] + I.t[JT_AREA_BYTES] > len) {
+		if (I.t[AH_JT_AREA_BYTES] != AH_JIT_AREA_BYTES || I.cb + I.t[AH_JT_JIT_AREA] + I.t[AH_JT_AREA_BYTES] > len) {
 			I.why = "compiled-program area out of range";
 			return;
 		}
@@ -181,7 +184,7 @@ asm_jit_emit(const dprog_host &xl, int mode, const std::vector<dp_map> &table,
 	     std::vector<unsigned char> *img_out, std::vector<unsigned char> *code,
 	     uint32_t *stack_stride, std::string *err)
 {
-	const uint32_t HDR = 16;
+	const uint32_t HDR = AH_JIT_ENTRY_OFF;
 	const jit_image &I = image_info(mode);
 	if (!I.ok) {
 		*err = I.why;
@@ -194,8 +197,8 @@ asm_jit_emit(const dprog_host &xl, int mode, const std::vector<dp_map> &table,
 	const size_t n = low.size();
 	const uint32_t *T = I.t;
 	auto tsize = [&](int a, int b) { return T[b] - T[a]; };
-	const uint32_t cs_len = tsize(JT_CS, JT_CS_END), cl_len = tsize(JT_CL, JT_CL_END);
-	const uint32_t jl_len = tsize(JT_JL, JT_JL_END);
+	const uint32_t cs_len = tsize(AH_JT_CS, AH_JT_CS_END), cl_len = tsize(AH_JT_CL, AH_JT_CL_END);
+	const uint32_t jl_len = tsize(AH_JT_JL, AH_JT_JL_END);
 
 	const std::vector<uint32_t> order = layout_order(xl, low);
 	std::vector<char> placed(n, 0);
@@ -311,7 +314,7 @@ asm_jit_emit(const dprog_host &xl, int mode, const std::vector<dp_map> &table,
 	const unsigned bus0 = cc_bus_violations();
 	if (getenv("EBPF_JIT_NOCC") == nullptr) {
 		cc_compile(xl, low, order, entry_point, mode, structured,
-			   cc_routines{T[JT_EXITK], T[JT_EXIT], T[JT_FAULT], T[JT_HLOOKUP]}, table, cb);
+			   cc_routines{T[AH_JT_EXIT_K], T[AH_JT_EXIT], T[AH_JT_FAULT], T[AH_JT_HLOOKUP]}, table, cb);
 	} else {
 		cb.assign(n, cc_block()); // every body copied: full group set-up
 		cc_prologue(mode, 0x7ff, true, false, cb[xl.start].prologue);
@@ -475,7 +478,7 @@ asm_jit_emit(const dprog_host &xl, int mode, const std::vector<dp_map> &table,
 			}
 			if (!structured && (ah_flags[h] & 1) && !long_cond[e] && cb[e].sdir != 0) {
 				const uint32_t br_at = pos[e] + be + (cb[e].sdir == 1 ? 0 : rev_cond[e] ? RC :
-								      T[JT_CS_BR] - T[JT_CS]);
+								      T[AH_JT_CS_BR] - T[AH_JT_CS]);
 				const uint32_t tk = xl.entries[e].target;
 				if (!fits_simm16((int64_t)pos[tk] - (int64_t)(br_at + 4))) {
 					long_cond[e] = 1;
@@ -506,14 +509,14 @@ asm_jit_emit(const dprog_host &xl, int mode, const std::vector<dp_map> &table,
 	// emit
 	std::vector<unsigned char> &img = *img_out;
 	img.assign(asm_image(mode), asm_image(mode) + asm_image_len(mode));
-	const size_t area = I.cb + T[JT_AREA];
+	const size_t area = I.cb + T[AH_JT_JIT_AREA];
 	const unsigned char *src = asm_image(mode) + I.cb;
 	// handler body h at area offset `at`; returns the bytes copied
 	auto copy_body = [&](size_t at, uint32_t h) -> uint32_t {
 		memcpy(&img[area + at], src + I.body_off[h], I.body_len[h]);
 		return I.body_len[h];
 	};
-	auto code_off = [&](uint32_t e) { return T[JT_AREA] + pos[e]; }; // from .Lcb
+	auto code_off = [&](uint32_t e) { return T[AH_JT_JIT_AREA] + pos[e]; }; // from .Lcb
 	auto put32 = [&](size_t at, uint32_t v) { memcpy(&img[area + at], &v, 4); };
 	auto copy_t = [&](size_t at, int a, uint32_t len) {
 		memcpy(&img[area + at], src + T[a], len);
@@ -531,10 +534,10 @@ asm_jit_emit(const dprog_host &xl, int mode, const std::vector<dp_map> &table,
 		size_t at = pos[e];
 		// (a long jump: s_add_u32 s60, s4, off; s_addc_u32 s61, s5, 0; s_setpc_b64 s[60:61])
 		auto long_jump = [&](size_t a, uint32_t target_pos) {
-			put32(a, 0x80000000u | (60u << 16) | (255u << 8) | 4u);
-			put32(a + 4, T[JT_AREA] + target_pos);
-			put32(a + 8, 0x80000000u | (0x04u << 23) | (61u << 16) | (128u << 8) | 5u);
-			put32(a + 12, 0xbe800000u | (0x1du << 8) | 60u);
+			put32(a, 0x80000000u | (S_JUNK << 16) | (255u << 8) | S_CB);
+			put32(a + 4, T[AH_JT_JIT_AREA] + target_pos);
+			put32(a + 8, 0x80000000u | (0x04u << 23) | ((S_JUNK + 1) << 16) | (128u << 8) | (S_CB + 1));
+			put32(a + 12, 0xbe800000u | (0x1du << 8) | S_JUNK);
 		};
 		auto sopp = [&](size_t a, uint32_t op, uint32_t target_pos) { // s_branch / s_cbranch_*
 			const int32_t d = ((int32_t)target_pos - (int32_t)(a + 4)) / 4;
@@ -572,11 +575,11 @@ asm_jit_emit(const dprog_host &xl, int mode, const std::vector<dp_map> &table,
 			}
 			uint32_t ic;
 			if (r != 2 && inline_code(v, &ic)) { // s_mov_b32 s(10+r), <inline constant>
-				put32(at, 0xbe800000u | ((uint32_t)(10 + r) << 16) | ic);
+				put32(at, 0xbe800000u | ((uint32_t)(AH_S_OPND + r) << 16) | ic);
 				at += 4;
 				continue;
 			}
-			copy_t(at, JT_MOV_S10 + r, 8);
+			copy_t(at, AH_JT_MOV_S10 + r, 8);
 			put32(at + 4, v);
 			at += 8;
 		}
@@ -598,7 +601,7 @@ asm_jit_emit(const dprog_host &xl, int mode, const std::vector<dp_map> &table,
 			memcpy(&img[area + at], b.data(), c.splice_at);
 			at += c.splice_at;
 			for (int r = 0; r < 2; r++) { // s_mov_b32 s(10 + r), literal
-				put32(at, 0xbe8000ffu | ((uint32_t)(10 + r) << 16));
+				put32(at, 0xbe8000ffu | ((uint32_t)(AH_S_OPND + r) << 16));
 				put32(at + 4, c.splice_sval[r]);
 				at += 8;
 			}
@@ -614,7 +617,7 @@ asm_jit_emit(const dprog_host &xl, int mode, const std::vector<dp_map> &table,
 		} else {
 			at += copy_body(at, h);
 			if (ah_flags[h] & 2) {
-				copy_t(at, JT_WAIT, 4);
+				copy_t(at, AH_JT_WAIT, 4);
 				at += 4;
 			}
 		}
@@ -641,11 +644,11 @@ asm_jit_emit(const dprog_host &xl, int mode, const std::vector<dp_map> &table,
 		} else if ((ah_flags[h] & 1) && cb[e].sdir == 1) { // statically taken by every lane
 			const uint32_t tk = xl.entries[e].target;
 			if (!long_cond[e]) {
-				copy_t(at, JT_BR, 4);
+				copy_t(at, AH_JT_BR, 4);
 				patch_simm16(at, pos[tk]);
 				at += 4;
 			} else {
-				copy_t(at, JT_JL, jl_len);
+				copy_t(at, AH_JT_JL, jl_len);
 				put32(at + 4, code_off(tk));
 				at += jl_len;
 			}
@@ -666,18 +669,18 @@ asm_jit_emit(const dprog_host &xl, int mode, const std::vector<dp_map> &table,
 				return !long_cond[e] && fits_simm16((int64_t)pos[tk] - (int64_t)(a + 4)) ? pos[tk]
 													 : (uint32_t)loop_at;
 			};
-			put32(at, 0x80000000u | (0x0du << 23) | (48u << 16) | (126u << 8) | 106u);
-			put32(at + 4, 0x80000000u | (0x13u << 23) | (18u << 16) | (106u << 8) | 126u);
+			put32(at, 0x80000000u | (0x0du << 23) | (S_MASK << 16) | (126u << 8) | 106u);
+			put32(at + 4, 0x80000000u | (0x13u << 23) | (S_SAVE << 16) | (106u << 8) | 126u);
 			sopp(at + 8, OP_SCC0, to_loop(at + 8));
-			put32(at + 12, 0xbe800000u | (126u << 16) | (0x01u << 8) | 18u);
-			put32(at + 16, 0x7e000000u | (41u << 17) | (0x01u << 9) | 255u);
+			put32(at + 12, 0xbe800000u | (126u << 16) | (0x01u << 8) | S_SAVE);
+			put32(at + 16, 0x7e000000u | ((uint32_t)AH_V_T << 17) | (0x01u << 9) | 255u);
 			put32(at + 20, code_off(nx));
-			put32(at + 24, 0xbe800000u | (126u << 16) | (0x01u << 8) | 48u);
+			put32(at + 24, 0xbe800000u | (126u << 16) | (0x01u << 8) | S_MASK);
 			sopp(at + 28, OP_EXECNZ, to_loop(at + 28));
-			put32(at + 32, 0x80000000u | (60u << 16) | (255u << 8) | 4u);
-			put32(at + 36, T[JT_SCHED]);
-			put32(at + 40, 0x80000000u | (0x04u << 23) | (61u << 16) | (128u << 8) | 5u);
-			put32(at + 44, 0xbe800000u | (0x1du << 8) | 60u);
+			put32(at + 32, 0x80000000u | (S_JUNK << 16) | (255u << 8) | S_CB);
+			put32(at + 36, T[AH_JT_SCHEDULE]);
+			put32(at + 40, 0x80000000u | (0x04u << 23) | ((S_JUNK + 1) << 16) | (128u << 8) | (S_CB + 1));
+			put32(at + 44, 0xbe800000u | (0x1du << 8) | S_JUNK);
 			at = loop_at;
 			if (!long_cond[e]) {
 				sopp(at, OP_BRANCH, pos[tk]);
@@ -689,25 +692,25 @@ asm_jit_emit(const dprog_host &xl, int mode, const std::vector<dp_map> &table,
 		} else if ((ah_flags[h] & 1) && cb[e].sdir < 0) {
 			const uint32_t tk = xl.entries[e].target;
 			if (!long_cond[e]) {
-				copy_t(at, JT_CS, cs_len);
-				patch_simm16(at + (T[JT_CS_BR] - T[JT_CS]), pos[tk]);
-				put32(at + (T[JT_CS_VT] - T[JT_CS]) + 4, code_off(tk));
+				copy_t(at, AH_JT_CS, cs_len);
+				patch_simm16(at + (T[AH_JT_CS_BR] - T[AH_JT_CS]), pos[tk]);
+				put32(at + (T[AH_JT_CS_VT] - T[AH_JT_CS]) + 4, code_off(tk));
 				at += cs_len;
 			} else {
-				copy_t(at, JT_CL, cl_len);
-				put32(at + (T[JT_CL_LIT] - T[JT_CL]) + 4, code_off(tk));
-				put32(at + (T[JT_CL_VT] - T[JT_CL]) + 4, code_off(tk));
+				copy_t(at, AH_JT_CL, cl_len);
+				put32(at + (T[AH_JT_CL_LIT] - T[AH_JT_CL]) + 4, code_off(tk));
+				put32(at + (T[AH_JT_CL_VT] - T[AH_JT_CL]) + 4, code_off(tk));
 				at += cl_len;
 			}
 		}
 		if (needs_branch(e)) {
 			const uint32_t sx = succ(e);
 			if (!long_br[e]) {
-				copy_t(at, JT_BR, 4);
+				copy_t(at, AH_JT_BR, 4);
 				patch_simm16(at, pos[sx]);
 				at += 4;
 			} else {
-				copy_t(at, JT_JL, jl_len);
+				copy_t(at, AH_JT_JL, jl_len);
 				put32(at + 4, code_off(sx));
 				at += jl_len;
 			}
@@ -729,10 +732,10 @@ asm_jit_emit(const dprog_host &xl, int mode, const std::vector<dp_map> &table,
 	}
 	if (structured) { // group end: every path has exited
 		const size_t a = end_pos;
-		put32(a, 0x80000000u | (60u << 16) | (255u << 8) | 4u);
-		put32(a + 4, T[JT_GDONE]);
-		put32(a + 8, 0x80000000u | (0x04u << 23) | (61u << 16) | (128u << 8) | 5u);
-		put32(a + 12, 0xbe800000u | (0x1du << 8) | 60u);
+		put32(a, 0x80000000u | (S_JUNK << 16) | (255u << 8) | S_CB);
+		put32(a + 4, T[AH_JT_GROUP_DONE]);
+		put32(a + 8, 0x80000000u | (0x04u << 23) | ((S_JUNK + 1) << 16) | (128u << 8) | (S_CB + 1));
+		put32(a + 12, 0xbe800000u | (0x1du << 8) | S_JUNK);
 	}
 	if (code)
 		code->assign(img.begin() + area, img.begin() + area + total);

@@ -305,8 +305,10 @@ launch(struct ebpf_prog *ep, dprog_device *dp, const dp_launch &L0, hipStream_t 
 	L.nmaps = dp->nmaps;
 	L.nentries = dp->nentries;
 	L.start = ep->xlated->start;
-	L.vflags = (ep->xlated->vstore_overlay ? 1u : 0u) | (ep->xlated->vstore_sites ? 2u : 0u) |
-		   (std::min<uint32_t>(ep->xlated->ovl_entries, 255u) << 8) | (L0.vflags & DP_VF_EXTENTS) |
+	L.vflags = (ep->xlated->vstore_overlay ? DP_VF_OVERLAY : 0u) |
+		   (ep->xlated->vstore_sites ? DP_VF_VSTORE : 0u) |
+		   (std::min<uint32_t>(ep->xlated->ovl_entries, DP_VF_ENTRIES_MAX) << DP_VF_ENTRIES_SHIFT) |
+		   (L0.vflags & DP_VF_EXTENTS) |
 		   (ep->xlated->write_cap ? DP_VF_WCAP : 0u);
 	launch_order order(ep->xlated->maps);
 	if ((err = sync_map_mirrors(ep, dp->device, stream)))
@@ -350,11 +352,11 @@ launch(struct ebpf_prog *ep, dprog_device *dp, const dp_launch &L0, hipStream_t 
 		// (gen_interp.py h_ldx_pktv), so the next group's DMA waits for the group's end
 		if (mode == 1 && ep->xlated->asm_keep)
 			L.vflags |= DP_VF_KEEP;
-		// general kernels: header staging (bit 31), and the headers kept in LDS too (bit 30;
+		// general kernels: header staging, and the headers kept in LDS too (DP_PKTLDS_HDRKEEP;
 		// when the 16 KB of packet buffers cost no resident workgroup: the VGPRs allow 6 per CU)
 		const bool hdrlds = ep->xlated->asm_hdrlds && asm_hdrlds_fits(dp->map_lds_bytes, L.stack_stride);
-		L.lds_pkt_base = mode != 0 ? 0 : hdrlds ? 0xc0000000u
-						 : ep->xlated->asm_gstage ? 0x80000000u : 0;
+		L.lds_pkt_base = mode != 0 ? 0 : hdrlds ? (DP_PKTLDS_HDRSTAGE | DP_PKTLDS_HDRKEEP)
+						 : ep->xlated->asm_gstage ? DP_PKTLDS_HDRSTAGE : 0;
 		unsigned long long *user_hist = L.hist;
 		if (L.hist) {
 			void *part = nullptr;

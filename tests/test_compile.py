@@ -331,7 +331,11 @@ def test_write_phasing_code(tmp_path):
     assert "ebpf_jit_s64w:" in m1 and "ebpf_jit_s64w" not in m0 + m3
     kds = dict(re.findall(r"\.amdhsa_kernel (\w+)\n(?:.*\n)*?\s*\.amdhsa_next_free_vgpr (\d+)", m1))
     assert kds["ebpf_jit_s64w"] == "96" and kds["ebpf_jit_s64"] == "80"
-    gen = open(os.path.join(root, "asm", "gen_interp.py")).read()
-    off = int(re.search(r"WPHASE_OFF = (0x[0-9a-f]+)", gen).group(1), 16)
-    hdr = open(os.path.join(root, "dprog.h")).read()
-    assert "offsetof(dp_launch, wphase) == 0x%x" % off in hdr
+    # the offset the kernels load wphase from is the one the generated header exports, and the
+    # build asserts that one against dprog.h's struct (asm_runtime.cpp)
+    hdr = open(out[3]).read()
+    off = int(re.search(r"#define AH_L_WPHASE (0x[0-9a-f]+)", hdr).group(1), 16)
+    assert len(re.findall(r"s_load_dword s99, s\[0:1\], 0x%x\n" % off, m1)) == 2   # both staged kernels
+    rt = open(os.path.join(root, "host", "asm_runtime.cpp")).read()
+    assert "X(wphase, AH_L_WPHASE)" in re.search(r"#define AH_LAUNCH_FIELDS\(X\) (.*)", hdr).group(1)
+    assert "static_assert(offsetof(dp_launch, member) == off," in rt and "\nAH_LAUNCH_FIELDS(X)\n" in rt
