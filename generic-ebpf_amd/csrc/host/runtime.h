@@ -1,5 +1,6 @@
 // runtime.h — what the files of the GPU backend share: gpu_runtime.cpp (programs, the launch),
-// stream_scratch.cpp, map_mirror.cpp, map_write_log.cpp, batch.cpp, and the launchers they call.
+// stream_scratch.cpp, map_mirror.cpp, map_write_log.cpp, batch.cpp, steer.cpp, and the launchers
+// they call.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,6 +30,7 @@ struct upd_owner {
 };
 int rows_acquire(int device, hipStream_t stream, void **out);
 int ovl_acquire(int device, hipStream_t stream, size_t bytes, uint8_t **out);
+int steer_acquire(int device, hipStream_t stream, size_t bytes, uint32_t **out);
 int upd_acquire(int device, hipStream_t stream, size_t log_bytes, size_t win_bytes, uint8_t **log,
 		unsigned long long **win, upd_owner *owner);
 void upd_settled(const upd_owner &o);

@@ -1,6 +1,6 @@
 // stream_scratch.cpp — scratch buffers kept per stream and device: the assembly kernels' verdict
 // partials, a map-writing batch's log and winner words, the spilled overlay, the multi-device
-// histogram rows.
+// histogram rows, the tile rows of a steering call.
 #include <dlfcn.h>
 
 #include <functional>
@@ -33,6 +33,10 @@ struct rows_slot {
 	// the portable interpreter's spilled overlays (dp_launch.ovl_spill), grown on demand
 	void *ovl = nullptr;
 	size_t ovl_bytes = 0;
+	// ebpf_batch_steer_dev's tile and segment rows (steer.hip), grown on demand (any contents:
+	// the count kernel writes every row the later kernels read)
+	void *steer = nullptr;
+	size_t steer_bytes = 0;
 	// ebpf_prog_run_batch_multi_dev, when this stream leads its device: one histogram row per
 	// shard on the device (any contents: every launch overwrites its row), and fork/join events
 	void *mh = nullptr;
@@ -178,6 +182,21 @@ ovl_acquire(int device, hipStream_t stream, size_t bytes, uint8_t **out)
 		err = grow(&r->ovl, &r->ovl_bytes, bytes, false, stream, &old.p[0]);
 	if (!err)
 		*out = static_cast<uint8_t *>(r->ovl);
+	return err;
+}
+
+// The stream's steering rows of at least `bytes` (any contents)
+int
+steer_acquire(int device, hipStream_t stream, size_t bytes, uint32_t **out)
+{
+	retired old;
+	std::lock_guard<std::mutex> g(g_rows_lock);
+	rows_slot *r;
+	int err = slot_for(device, stream, &r);
+	if (!err)
+		err = grow(&r->steer, &r->steer_bytes, bytes, false, stream, &old.p[0]);
+	if (!err)
+		*out = static_cast<uint32_t *>(r->steer);
 	return err;
 }
 

@@ -124,6 +124,9 @@ FUNCS = {
     "ebpf_pcap_extents": (_I, [_VP, ctypes.c_size_t, _I, _VP, _VP]),
     "ebpf_prog_run_batch_async": (_I, [_VP, _VP, _VP, _VP, ctypes.POINTER(_VP)]),
     "ebpf_batch_wait": (_I, [_VP, _VP]),
+    "ebpf_batch_steer": (_I, [_VP, _VP, _U64, _VP, _VP]),
+    "ebpf_batch_steer_dev": (_I, [_I, _VP, _VP, _U64, _VP, _VP, _VP]),
+    "ebpf_batch_select_dev": (_I, [_I, _VP, _VP, _U64, _VP, _VP]),
 }
 DATA_SYMBOLS = ["emt_array", "emt_percpu_array", "emt_hashtable", "emt_percpu_hashtable",
                 "eht_map_lookup_elem", "eht_map_update_elem", "eht_map_delete_elem"]
@@ -133,6 +136,8 @@ _lib = None
 
 BATCH_HIST_OVERWRITE = 0x1  # include/ebpf_gpu.h EBPF_BATCH_HIST_OVERWRITE
 BATCH_EXTENTS = 0x2         # EBPF_BATCH_EXTENTS: offsets holds (start, end) pairs
+STEER_STARTS = EBPF_HIST_BINS + 1  # EBPF_STEER_STARTS: entries of a steering call's starts
+STEER_TILE = 4096           # csrc/host/steer.h STEER_TILE: packets per workgroup of the kernels
 
 
 class _AsyncJob:
@@ -524,6 +529,38 @@ def time_next_launch(start_event, stop_event):
     """The calling thread's next run_batch_dev records these hipEvent_t handles (ints, or None
     to cancel) around the interpreter kernel alone (include/ebpf_gpu.h)."""
     _check(lib().ebpf_gpu_time_next_launch(start_event, stop_event), "ebpf_gpu_time_next_launch")
+
+
+def steer(ret, faults=None):
+    """ebpf_batch_steer on host arrays: (index u32[count], starts u64[STEER_STARTS]);
+    index[starts[b]:starts[b + 1]] are the packets of verdict class b, in ascending order."""
+    ret = np.ascontiguousarray(ret, dtype=np.uint64)
+    if faults is not None:
+        faults = np.ascontiguousarray(faults, dtype=np.uint8)
+        assert len(faults) == len(ret)
+    index = np.zeros(len(ret), dtype=np.uint32)
+    starts = np.zeros(STEER_STARTS, dtype=np.uint64)
+    _check(lib().ebpf_batch_steer(ret.ctypes.data if len(ret) else None,
+                                  None if faults is None or not len(ret) else faults.ctypes.data,
+                                  len(ret), index.ctypes.data if len(ret) else None,
+                                  starts.ctypes.data), "ebpf_batch_steer")
+    return index, starts
+
+
+def steer_dev(device, ret_ptr, faults_ptr, count, index_ptr, starts_ptr, stream=None):
+    """ebpf_batch_steer_dev: device pointers (ints); asynchronous on ``stream``."""
+    _check(lib().ebpf_batch_steer_dev(device, ret_ptr, faults_ptr, count, index_ptr, starts_ptr,
+                                      stream), "ebpf_batch_steer_dev")
+
+
+def select_dev(device, data_ptr, count, stride, index_ptr, n, extents_ptr, offsets_ptr=None,
+               stream=None, extents=False):
+    """ebpf_batch_select_dev: the (start, end) pairs of packets index[0..n) of the batch
+    (data_ptr, count, stride, offsets_ptr, extents) as run_batch_dev takes it, written to
+    ``extents_ptr`` (2n u64); device pointers (ints); asynchronous on ``stream``."""
+    b = PktBatch(data_ptr, offsets_ptr, count, stride, BATCH_EXTENTS if extents else 0)
+    _check(lib().ebpf_batch_select_dev(device, ctypes.byref(b), index_ptr, n, extents_ptr,
+                                       stream), "ebpf_batch_select_dev")
 
 
 def set_variant(v):

@@ -282,6 +282,58 @@ int ebpf_prog_run_batch_multi_dev(struct ebpf_prog *ep, int ndev, const int *dev
 				  uint8_t *const *faults_dev, uint64_t *const *hist_dev,
 				  void *const *streams);
 
+/* Steering a batch by verdict: the step after ret[] for a caller that acts on verdicts (a switch
+ * whose verdict is the destination port, a classifier, a drop / pass filter).  The histogram
+ * says how many packets went to each class; these functions say which, without per-packet data
+ * crossing to the host:
+ *
+ *   ebpf_prog_run_batch_dev(ep, dev, &batch, ret, faults, hist, s);
+ *   ebpf_batch_steer_dev(dev, ret, faults, batch.count, index, starts, s);
+ *   (read starts — 258 words — or a class's two entries)
+ *   ebpf_batch_select_dev(dev, &batch, index + starts[b], starts[b+1] - starts[b], extents, s);
+ *   sub = {batch.data, extents, starts[b+1] - starts[b], 0, EBPF_BATCH_EXTENTS};
+ *   ebpf_prog_run_batch_dev(ep2, dev, &sub, ret2, faults2, hist2, s);
+ *
+ * Classes are the histogram's bins: packet i is of class 256 if faults is given and faults[i]
+ * != 0, else of class min(ret[i], 255).  A faulted packet's ret is 0, so without faults
+ * (NULL) faulted packets fall into class 0 together with the packets that returned 0.
+ * The result is a stable partition: index[starts[b] .. starts[b+1]) holds the packets of class b
+ * in ascending order; starts has EBPF_STEER_STARTS entries, starts[0] = 0 and
+ * starts[EBPF_HIST_BINS] = count, so starts[b+1] - starts[b] is bin b of the histogram.  It is
+ * a function of ret / faults alone: two calls on the same input give the same bytes.
+ *
+ * ebpf_batch_steer: host buffers, a plain counting sort; no GPU needed (the results of
+ *   ebpf_prog_run_batch, and the statement of what the device function computes).
+ * ebpf_batch_steer_dev: every pointer is device memory on `device`; enqueued on `stream`
+ *   (hipStream_t, NULL = default stream), returns without synchronising; after the program's
+ *   launch on the same stream it reads what that launch wrote.  Temporary storage is the
+ *   library's, per stream, grown on demand (1 KiB per 4,096 packets).  ret_dev and starts_dev
+ *   must be 8-byte aligned, index_dev 4-byte aligned, as their types say.
+ * Both return 0; EINVAL for a NULL starts, or a NULL ret or index with count > 0 (count == 0:
+ * starts becomes all zeros); E2BIG for count > 0xffffffff (the packet index is 32 bits).  The
+ * device function then returns ENODEV (no GPU, or no such device), ENOMEM (no scratch) or EIO.
+ *
+ * ebpf_batch_select_dev: a list of n packets of `batch` (any list: a class of a steered batch,
+ *   several classes, a list of the caller's own) as an extents batch over the same data.  For
+ *   j < n, extents_dev[2j], extents_dev[2j+1] = (start, end) of packet index_dev[j] relative to
+ *   batch->data, whatever form `batch` has: i * stride and (i + 1) * stride, offsets[i] and
+ *   offsets[i+1], or the pair offsets[2i], offsets[2i+1] as it stands.  An index >= batch->count
+ *   gives (0, 0), a packet of length 0.  {batch->data, extents_dev, n, 0, EBPF_BATCH_EXTENTS} is
+ *   then a batch for any entry point that takes device pointers; no packet byte is moved.  An
+ *   extents batch runs on the general kernels even when `batch` was a 16-byte-aligned
+ *   64-byte-stride batch that took the staged kernel.  batch->offsets, index_dev and extents_dev
+ *   are device memory on `device`; batch->data is not read.  Asynchronous on `stream` as above.
+ *   Returns 0; EINVAL (a batch that the run functions would refuse, or a NULL index or extents
+ *   with n > 0); ENODEV; EIO.
+ * None of the three changes the calling thread's current HIP device. */
+#define EBPF_STEER_STARTS (EBPF_HIST_BINS + 1)
+int ebpf_batch_steer(const uint64_t *ret, const uint8_t *faults, uint64_t count, uint32_t *index,
+		     uint64_t *starts);
+int ebpf_batch_steer_dev(int device, const uint64_t *ret_dev, const uint8_t *faults_dev,
+			 uint64_t count, uint32_t *index_dev, uint64_t *starts_dev, void *stream);
+int ebpf_batch_select_dev(int device, const struct ebpf_pkt_batch *batch, const uint32_t *index_dev,
+			  uint64_t n, uint64_t *extents_dev, void *stream);
+
 /* Select the device used by ebpf_prog_run_batch for the calling thread. */
 int ebpf_gpu_set_device(int device);
 
