@@ -143,51 +143,60 @@ ALU32I = ["ADD", "SUB", "MUL", "OR", "AND", "XOR", "LSH", "RSH", "MOV", "DIV", "
 CONDS = ["JEQ", "JNE", "JGT", "JGE", "JLT", "JLE", "JSGT", "JSGE", "JSLT", "JSLE", "JSET"]
 SIZES = [1, 2, 4, 8]
 
-FAMILIES = []   # (name, arity) arity: 2 = (dst, src), 1 = (reg), 0
+# (name, arity, class, index) arity: 2 = (dst, src), 1 = (reg), 0.  The class groups the families
+# the host compiler treats alike (asm_cc.cpp reads ah_fam_class / ah_fam_idx, never the order of
+# the registrations below); the index within it is the ALU operation's position in its list, the
+# condition's position in CONDS, or log2 of the access size in bytes.  A family registered
+# without a class is a class of its own.
+FAMILIES = []
 
 
-def fam(name, arity):
-    FAMILIES.append((name, arity))
+def fam(name, arity, cls=None, idx=0):
+    FAMILIES.append((name, arity, cls or name, idx))
 
 
-for o in ALU64R:
-    fam("A64R_" + o, 2)
-for o in ALU32R:
-    fam("A32R_" + o, 2)
-for c in CONDS:
-    fam(c + "_R", 2)
+def lg2(z):
+    return z.bit_length() - 1
+
+
+for i, o in enumerate(ALU64R):
+    fam("A64R_" + o, 2, "A64R", i)
+for i, o in enumerate(ALU32R):
+    fam("A32R_" + o, 2, "A32R", i)
+for i, c in enumerate(CONDS):
+    fam(c + "_R", 2, "JR", i)
 for z in SIZES:
-    fam("LDXGEN%d" % z, 2)
+    fam("LDXGEN%d" % z, 2, "LDXGEN", lg2(z))
 for z in SIZES:
-    fam("STXGEN%d" % z, 2)
+    fam("STXGEN%d" % z, 2, "STXGEN", lg2(z))
 for z in SIZES:
-    fam("LDXMAP%d" % z, 2)
-for o in ALU64I:
-    fam("A64I_" + o, 1)
-for o in ALU32I:
-    fam("A32I_" + o, 1)
+    fam("LDXMAP%d" % z, 2, "LDXMAP", lg2(z))
+for i, o in enumerate(ALU64I):
+    fam("A64I_" + o, 1, "A64I", i)
+for i, o in enumerate(ALU32I):
+    fam("A32I_" + o, 1, "A32I", i)
 for w in (16, 32, 64):
-    fam("BSWAP%d" % w, 1)
-for c in CONDS:
-    fam(c + "_I", 1)
+    fam("BSWAP%d" % w, 1, "BSWAP", lg2(w // 8))
+for i, c in enumerate(CONDS):
+    fam(c + "_I", 1, "JI", i)
 for z in SIZES:
-    fam("LDXPKTG%d" % z, 1)
+    fam("LDXPKTG%d" % z, 1, "LDXPKTG", lg2(z))
 for z in SIZES:
-    fam("LDXSTK%d" % z, 1)
+    fam("LDXSTK%d" % z, 1, "LDXSTK", lg2(z))
 for z in SIZES:
-    fam("STXSTK%d" % z, 1)
+    fam("STXSTK%d" % z, 1, "STXSTK", lg2(z))
 for z in SIZES:
-    fam("STGEN%d" % z, 1)
+    fam("STGEN%d" % z, 1, "STGEN", lg2(z))
 for z in SIZES:
-    fam("STSTK%d" % z, 0)
+    fam("STSTK%d" % z, 0, "STSTK", lg2(z))
 for n in ("EXIT", "FAULT", "NOP", "LOOKUPSTK", "LOOKUPGEN"):
     fam(n, 0)
-for z in SIZES:
-    fam("LDXPKC%d" % z, 3)      # staged packet load at a constant byte offset: (dst, offset)
+for z in SIZES:                # staged packet load at a constant byte offset: (dst, offset)
+    fam("LDXPKC%d" % z, 3, "LDXPKC", lg2(z))
 fam("HLOOKUP", 0)              # hashtable lookup, map known at translation time (s14 = record offset)
 fam("UPDATE", 0)               # map_update_elem, map known (s14 = record offset, s15 = entry index)
-for z in SIZES:
-    fam("LDXHV%d" % z, 2)       # load from a hashtable value (lookup result), in range by provenance
+for z in SIZES:                # load from a hashtable value (lookup result), in range by provenance
+    fam("LDXHV%d" % z, 2, "LDXHV", lg2(z))
 # standard-eBPF semantics (ebpf_prog_set_semantics): the operations whose meaning differs from
 # the reference's, and the JMP32 class
 fam("MOV64R", 2)
@@ -199,10 +208,10 @@ fam("ARSH32I", 1)
 fam("ARSH32R", 2)
 for o in ("DIV64Z", "MOD64Z", "DIV32Z", "MOD32Z"):
     fam(o, 2)                  # register divisor; zero gives 0 (DIV) or dst (MOD)
-for c in CONDS:
-    fam("J32" + c[1:] + "_R", 2)
-for c in CONDS:
-    fam("J32" + c[1:] + "_I", 1)
+for i, c in enumerate(CONDS):
+    fam("J32" + c[1:] + "_R", 2, "J32R", i)
+for i, c in enumerate(CONDS):
+    fam("J32" + c[1:] + "_I", 1, "J32I", i)
 # loops under standard semantics (dprog.h DK_LOOPINIT / DK_LOOPCNT): the lane's count of taken
 # backward jumps in the first 4 bytes of its stack slice (below the frame the program addresses)
 fam("LOOPINIT", 0)
@@ -210,32 +219,32 @@ fam("LOOPCNT", 0)
 fam("HDELETE", 0)              # map_delete_elem on a hashtable known at translation time (s14, s15)
 # interpreter superinstructions (asm_runtime.cpp asm_fuse_interp; staged kernels): a packet load at
 # a constant offset fused with the BE16 / BE32 of its destination (dst, offset)
-fam("LDXPKBE16", 3)
-fam("LDXPKBE32", 3)
+fam("LDXPKBE16", 3, "LDXPKBE", 1)
+fam("LDXPKBE32", 3, "LDXPKBE", 2)
 # stores into map values (ebpf_gpu.h "Stores into map values"; dprog.h DK_CNT_STORE / DK_XADD):
 # the STX of a counter update (d = the pointer, s = the value), XADD (d = the pointer, s = the
 # addend) and XADD | FETCH (d = the addend, which receives the old value; s = the pointer)
 for z in (4, 8):
-    fam("CNTST%d" % z, 2)
+    fam("CNTST%d" % z, 2, "CNTST", lg2(z))
 for z in (4, 8):
-    fam("XADD%d" % z, 2)
+    fam("XADD%d" % z, 2, "XADD", lg2(z))
 for z in (4, 8):
-    fam("XADDF%d" % z, 2)
+    fam("XADDF%d" % z, 2, "XADDF", lg2(z))
 fam("OVLINIT", 0)              # dprog.h DK_OVLINIT: the lane's overlay and write counts = 0
 # a counter update the translator resolved completely (asm_runtime.cpp): an immediate addend
 # (s[10:11]) into a DP_MAP_ATOMIC map's delta area at r_d + s14 (d = the value pointer, a
 # non-NULL lookup result; s14 = the offset + the map's delta-area offset)
 for z in (4, 8):
-    fam("CNTAI%d" % z, 1)
+    fam("CNTAI%d" % z, 1, "CNTAI", lg2(z))
 # ... into the workgroup's LDS sums of a DP_MAP_LDSDELTA map: at (r_d - s15) + s14 (s15 = the
 # mirror's address, low word; s14 = the offset + the table's LDS address)
 for z in (4, 8):
-    fam("CNTAL%d" % z, 1)
+    fam("CNTAL%d" % z, 1, "CNTAL", lg2(z))
 # a load through a packet pointer at an offset only known at run time (translate.cpp AV_CTXV:
 # a cursor advanced in a loop): one bounds check against the lane's packet, one load; lanes whose
 # address leaves the packet take the generic path (s[10:11] = the offset)
 for z in SIZES:
-    fam("LDXPKTV%d" % z, 2)
+    fam("LDXPKTV%d" % z, 2, "LDXPKTV", lg2(z))
 SPILL = 51                     # v51 (H[5]): .Lr_check's SGPR spill lanes around .Lr_vstore
 
 # ---------------------------------------------------------------- the ABI shared with the host
@@ -3332,6 +3341,30 @@ def main():
         f.write("\n".join(header) + "\n")
 
 
+def header_families():
+    """The family structure the host compiler reads: per family its class (AHC_*) and its index
+    within the class, and the names of the condition indices."""
+    classes = []
+    for _, _, cls, _ in FAMILIES:
+        if cls not in classes:
+            classes.append(cls)
+    for cls in classes:   # an index names one family of its class
+        idx = [i for _, _, c, i in FAMILIES if c == cls]
+        assert len(set(idx)) == len(idx), "class %s: index used twice" % cls
+    h = ["#define AHF_COUNT %d" % len(FAMILIES),
+         "// family classes: the families the code generator treats alike (asm_cc.cpp)",
+         "enum { %s, AHC_COUNT };" % ", ".join("AHC_" + c for c in classes),
+         "// per family: class (AHC_*), index within the class (the ALU operation, the condition",
+         "// AH_CC_*, log2 of the access size in bytes)",
+         "static const uint8_t ah_fam_class[AHF_COUNT] = {%s};" % ",".join(
+             str(classes.index(c)) for _, _, c, _ in FAMILIES),
+         "static const uint8_t ah_fam_idx[AHF_COUNT] = {%s};" % ",".join(
+             str(i) for _, _, _, i in FAMILIES),
+         "// condition indices of the conditional-jump classes (JR, JI, J32R, J32I)"]
+    h += ["#define AH_CC_%s %d" % (c, i) for i, c in enumerate(CONDS)]
+    return h
+
+
 def generate(out_s, staged_image):
     global STAGED_IMAGE
     STAGED_IMAGE = staged_image
@@ -3347,7 +3380,7 @@ def generate(out_s, staged_image):
     header = ["// generated by gen_interp.py — handler family ids for asm_runtime.cpp",
               "#pragma once", "#include <stdint.h>", "#define AH_NREGS %d" % NREG]
     fam_of, dst_of, src_of = [], [], []
-    for fi, (name, arity) in enumerate(FAMILIES):
+    for fi, (name, arity, _, _) in enumerate(FAMILIES):
         header.append("#define AH_%s %d" % (name, hid))
         header.append("#define AHF_%s %d" % (name, fi))
         for d, sr in variants(arity):
@@ -3403,6 +3436,7 @@ def generate(out_s, staged_image):
     header.append("static const uint8_t ah_fam[AH_COUNT] = {%s};" % ",".join(map(str, fam_of)))
     header.append("static const uint8_t ah_dst[AH_COUNT] = {%s};" % ",".join(map(str, dst_of)))
     header.append("static const uint8_t ah_src[AH_COUNT] = {%s};" % ",".join(map(str, src_of)))
+    header += header_families()
     header += header_abi()
     header.append("#define AH_JIT_AREA_BYTES %d" % JIT_AREA_BYTES)
     header.append("#define AH_S_JOIN %d  // structured programs: taken-lane masks s[74:75]..  (staged image)" % S_JOIN)

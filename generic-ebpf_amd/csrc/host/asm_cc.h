@@ -39,16 +39,43 @@ struct cc_routines {
 	uint32_t hlookup; // HLOOKUP: r0 = hashtable lookup (record offset s14, key at r2)
 };
 
+// The A/B and debugging switches of the host compiler: every environment variable it reads
+// (besides EBPF_CC_BUS_DEBUG, which only prints).  asm_jit_emit reads them once per compilation
+// (cc_read_options) and passes them down; tests flip them between two compilations in a process.
+enum : unsigned { // EBPF_CC_OFF bits
+	CC_OFF_DEAD = 1,          // no dead-code removal (and no MOV fusing, every register zeroed)
+	CC_OFF_ZERO_ALL = 2,      // zero every register at the start
+	CC_OFF_STACK_FWD = 4,     // no stack store-to-load forwarding
+	CC_OFF_LOOKUP = 8,        // no lookup specialisation
+	CC_OFF_STATIC_TAKEN = 16, // a compare decided as taken still sets VCC and branches on it
+	CC_OFF_EXIT_KNOWN = 32,   // no known-r0 exits
+};
+struct cc_options {
+	unsigned off = 0;          // EBPF_CC_OFF: CC_OFF_* bits
+	bool runmask = true;       // EBPF_CC_NORUNMASK=1 clears: hoisted loads compare per load
+	bool hoist = true;         // EBPF_CC_NOHOIST=1 clears: general-kernel packet loads in place
+	bool short_mask = true;    // EBPF_CC_NOSHORT=1 clears: general LDXPKC copies the handler body
+	bool exit_call = false;    // EBPF_CC_EXITCALL=1 sets: structured exits call .Lr_exit
+	bool pktv = true;          // EBPF_CC_NOPKTV=1 clears: LDXPKTV copies the handler body
+	bool hash_forward = true;  // EBPF_CC_NOHFWD=1 clears: no value bytes kept from a hashtable probe
+	bool drop_stores = true;   // EBPF_CC_KEEPSTORES=1 clears: stack stores nothing reads stay
+	bool compile = true;       // EBPF_JIT_NOCC=1 clears: every entry copies its handler body
+	bool structured = true;    // EBPF_JIT_NOSTRUCT=1 clears: parking scheduler everywhere
+	bool reverse_loops = true; // EBPF_JIT_NOREVLOOP=1 clears: loop back edges split forwards
+};
+cc_options cc_read_options();
+
+// VOP3 instructions emitted with two SGPR sources so far on this thread (must stay 0)
+unsigned cc_bus_violations();
+
 // low: the lowered entries (asm_lower); order: the layout order (depth-first, parents first);
 // entry_point[e]: e can be entered other than by falling through from its layout predecessor.
 // mode 1 = staged 64-B packets (packet loads read v22..v37).  structured: the program runs with
 // structured control flow (asm_jit.cpp): exits and faults are calls that return, compares
-// always leave VCC.  table: the program's maps.
-// VOP3 instructions emitted with two SGPR sources so far on this thread (must stay 0)
-unsigned cc_bus_violations();
+// always leave VCC.  table: the program's maps.  opt: the switches.
 void cc_compile(const dprog_host &xl, const std::vector<dp_entry> &low, const std::vector<uint32_t> &order,
 		const std::vector<char> &entry_point, int mode, bool structured, const cc_routines &rt,
-		const std::vector<dp_map> &table, std::vector<cc_block> &out);
+		const std::vector<dp_map> &table, const cc_options &opt, std::vector<cc_block> &out);
 
 // The group set-up a compiled program does itself (the kernel jumps straight to it): the packet
 // address (staged mode), r1 = packet, r10 = stack top, zeroes for r0, r2..r9 — the registers in

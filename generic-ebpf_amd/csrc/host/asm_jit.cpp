@@ -25,6 +25,7 @@
 
 #include "asm_cc.h"
 #include "asm_handlers.h"
+#include "gfx950_enc.h"
 #include "runtime.h"
 
 int asm_lower(const dprog_host &xl, int mode, const std::vector<dp_map> &table,
@@ -37,9 +38,6 @@ static_assert(AH_S_OPND == 10 && AH_JT_MOV_S11 == AH_JT_MOV_S10 + 1 && AH_JT_MOV
 		      AH_JT_MOV_S13 == AH_JT_MOV_S10 + 3 && AH_JT_MOV_S14 == AH_JT_MOV_S10 + 4 &&
 		      AH_JT_MOV_S15 == AH_JT_MOV_S10 + 5,
 	      "the s_mov templates of the operand registers s10..s15 are consecutive");
-
-// SOP1 / SOP2 / VOP1 words of the glue encoded here (exec = 126, vcc = 106, literal = 255)
-constexpr uint32_t S_JUNK = AH_S_JUNK, S_CB = AH_S_CB, S_MASK = AH_S_MASK, S_SAVE = AH_S_SAVE;
 
 struct jit_image {
 	bool ok = false;
@@ -185,6 +183,7 @@ asm_jit_emit(const dprog_host &xl, int mode, const std::vector<dp_map> &table,
 	     uint32_t *stack_stride, std::string *err)
 {
 	const uint32_t HDR = AH_JIT_ENTRY_OFF;
+	const cc_options opt = cc_read_options(); // (per call: tests change the environment in between)
 	const jit_image &I = image_info(mode);
 	if (!I.ok) {
 		*err = I.why;
@@ -244,7 +243,7 @@ asm_jit_emit(const dprog_host &xl, int mode, const std::vector<dp_map> &table,
 	for (uint32_t e = 0; e < n; e++)
 		if (xl.entries[e].kind == DK_LOOPCNT && xl.entries[e].next < n)
 			loop_head[xl.entries[e].next] = 1;
-	if (getenv("EBPF_JIT_NOREVLOOP") == nullptr)
+	if (opt.reverse_loops)
 		for (uint32_t e : order) {
 			const uint32_t h = (uint32_t)low[e].handler;
 			if (!(ah_flags[h] & 1))
@@ -267,8 +266,7 @@ asm_jit_emit(const dprog_host &xl, int mode, const std::vector<dp_map> &table,
 	std::vector<uint32_t> cont(n, GROUP_END); // where a path through the entry continues
 	std::vector<int> jdepth(n, 0);            // pending branches (join masks in use)
 	std::vector<int> join_of(n, -1);          // entry e is the taken block of conditional k
-	bool structured = (mode == 1 || AH_GEN_JOIN) && getenv("EBPF_JIT_NOSTRUCT") == nullptr &&
-			  getenv("EBPF_JIT_NOCC") == nullptr;
+	bool structured = (mode == 1 || AH_GEN_JOIN) && opt.structured && opt.compile;
 	for (uint32_t e : order) {
 		const uint32_t h = (uint32_t)low[e].handler;
 		if (h == (uint32_t)AH_LOOKUPGEN)
@@ -312,9 +310,9 @@ asm_jit_emit(const dprog_host &xl, int mode, const std::vector<dp_map> &table,
 	// per entry: optimised code (asm_cc.cpp) or the interpreter's handler body
 	std::vector<cc_block> cb;
 	const unsigned bus0 = cc_bus_violations();
-	if (getenv("EBPF_JIT_NOCC") == nullptr) {
+	if (opt.compile) {
 		cc_compile(xl, low, order, entry_point, mode, structured,
-			   cc_routines{T[AH_JT_EXIT_K], T[AH_JT_EXIT], T[AH_JT_FAULT], T[AH_JT_HLOOKUP]}, table, cb);
+			   cc_routines{T[AH_JT_EXIT_K], T[AH_JT_EXIT], T[AH_JT_FAULT], T[AH_JT_HLOOKUP]}, table, opt, cb);
 	} else {
 		cb.assign(n, cc_block()); // every body copied: full group set-up
 		cc_prologue(mode, 0x7ff, true, false, cb[xl.start].prologue);
@@ -370,23 +368,11 @@ asm_jit_emit(const dprog_host &xl, int mode, const std::vector<dp_map> &table,
 	}
 	// s_mov_b32 s(10+r), v: 4 bytes with an inline constant, else 8 (s12, the resume offset,
 	// is only known after layout: always the literal form)
-	auto inline_code = [](uint32_t v, uint32_t *code) {
-		const int32_t x = (int32_t)v;
-		if (x >= 0 && x <= 64) {
-			*code = 128 + (uint32_t)x;
-			return true;
-		}
-		if (x >= -16 && x < 0) {
-			*code = 192 + (uint32_t)(-x);
-			return true;
-		}
-		return false;
-	};
 	auto pre_len = [&](uint32_t e) {
 		uint32_t sz = 0, c;
 		for (int r = 0; r < 6; r++)
 			if (pre_mask[e] & (1u << r))
-				sz += (r != 2 && inline_code(sval_of(e, r), &c)) ? 4 : 8;
+				sz += (r != 2 && inline_i64((int32_t)sval_of(e, r), &c)) ? 4 : 8;
 		return sz;
 	};
 	// structured-mode glue (SALU, encoded here): join head, conditional split, leaf continuation
@@ -506,65 +492,62 @@ asm_jit_emit(const dprog_host &xl, int mode, const std::vector<dp_map> &table,
 			return EINVAL;
 		}
 
-	// emit
+	// emit: each block is built in a buffer (glue encoded by gfx950_enc.h, bodies and templates
+	// copied from the image) and copied to its place in the area
 	std::vector<unsigned char> &img = *img_out;
 	img.assign(asm_image(mode), asm_image(mode) + asm_image_len(mode));
 	const size_t area = I.cb + T[AH_JT_JIT_AREA];
 	const unsigned char *src = asm_image(mode) + I.cb;
-	// handler body h at area offset `at`; returns the bytes copied
-	auto copy_body = [&](size_t at, uint32_t h) -> uint32_t {
-		memcpy(&img[area + at], src + I.body_off[h], I.body_len[h]);
-		return I.body_len[h];
-	};
 	auto code_off = [&](uint32_t e) { return T[AH_JT_JIT_AREA] + pos[e]; }; // from .Lcb
-	auto put32 = [&](size_t at, uint32_t v) { memcpy(&img[area + at], &v, 4); };
-	auto copy_t = [&](size_t at, int a, uint32_t len) {
-		memcpy(&img[area + at], src + T[a], len);
+	std::vector<uint8_t> g;
+	enc G{g};
+	auto append = [&](const void *p, size_t len) {
+		g.insert(g.end(), static_cast<const uint8_t *>(p), static_cast<const uint8_t *>(p) + len);
 	};
-	auto patch_simm16 = [&](size_t at, uint32_t target) {
-		uint32_t w;
-		memcpy(&w, &img[area + at], 4);
-		const int32_t d = ((int32_t)target - (int32_t)(at + 4)) / 4;
-		w = (w & 0xffff0000u) | ((uint32_t)d & 0xffffu);
-		memcpy(&img[area + at], &w, 4);
+	auto copy_body = [&](uint32_t h) { append(src + I.body_off[h], I.body_len[h]); };
+	auto copy_t = [&](int a, uint32_t len) -> size_t { // a glue template; returns its offset in g
+		const size_t at = g.size();
+		append(src + T[a], len);
+		return at;
 	};
+	auto put32 = [&](size_t at, uint32_t v) { memcpy(&g[at], &v, 4); }; // data into a template
 	for (uint32_t e : order) {
-		const dp_entry &o = low[e];
-		const uint32_t h = (uint32_t)o.handler;
-		size_t at = pos[e];
-		// (a long jump: s_add_u32 s60, s4, off; s_addc_u32 s61, s5, 0; s_setpc_b64 s[60:61])
-		auto long_jump = [&](size_t a, uint32_t target_pos) {
-			put32(a, 0x80000000u | (S_JUNK << 16) | (255u << 8) | S_CB);
-			put32(a + 4, T[AH_JT_JIT_AREA] + target_pos);
-			put32(a + 8, 0x80000000u | (0x04u << 23) | ((S_JUNK + 1) << 16) | (128u << 8) | (S_CB + 1));
-			put32(a + 12, 0xbe800000u | (0x1du << 8) | S_JUNK);
+		const uint32_t h = (uint32_t)low[e].handler;
+		g.clear();
+		// branch distances are counted from the block's place in the area
+		auto simm16_to = [&](size_t at, uint32_t target_pos) -> uint32_t {
+			return (uint32_t)(((int32_t)target_pos - (int32_t)(pos[e] + at + 4)) / 4) & 0xffffu;
 		};
-		auto sopp = [&](size_t a, uint32_t op, uint32_t target_pos) { // s_branch / s_cbranch_*
-			const int32_t d = ((int32_t)target_pos - (int32_t)(a + 4)) / 4;
-			put32(a, 0xbf800000u | (op << 16) | ((uint32_t)d & 0xffffu));
+		auto branch = [&](uint32_t op, uint32_t target_pos) { // s_branch / s_cbranch_*
+			G.sopp(op, simm16_to(g.size(), target_pos));
 		};
-		const uint32_t OP_BRANCH = 0x02, OP_SCC0 = 0x04, OP_EXECZ = 0x08, OP_EXECNZ = 0x09;
+		auto patch_simm16 = [&](size_t at, uint32_t target_pos) { // the branch of a template
+			const uint32_t d = simm16_to(at, target_pos);
+			g[at] = (uint8_t)d;
+			g[at + 1] = (uint8_t)(d >> 8);
+		};
+		// a branch where it reaches, else the inverse branch over a long jump
+		auto branch_or_jump = [&](bool far, uint32_t op, uint32_t op_inverse, uint32_t target_pos) {
+			if (!far) {
+				branch(op, target_pos);
+				return;
+			}
+			G.sopp(op_inverse, LJ / 4);
+			G.long_jump(T[AH_JT_JIT_AREA] + target_pos);
+		};
+		auto jump = [&](bool far, uint32_t target_pos) {
+			if (far)
+				G.long_jump(T[AH_JT_JIT_AREA] + target_pos);
+			else
+				branch(SP_BRANCH, target_pos);
+		};
 		if (structured && join_of[e] >= 0) {
 			const uint32_t sk = AH_S_JOIN + 2 * (uint32_t)jdepth[join_of[e]];
-			put32(at, 0xbe800000u | (126u << 16) | (0x01u << 8) | sk); // s_mov_b64 exec, s[Tk]
-			at += 4;
-			if (!long_join[e]) {
-				sopp(at, OP_EXECZ, cont_pos(cont[e]));
-				at += 4;
-			} else {
-				put32(at, 0xbf800000u | (OP_EXECNZ << 16) | (LJ / 4));
-				long_jump(at + 4, cont_pos(cont[e]));
-				at += 4 + LJ;
-			}
+			G.sop1(S1_MOV_B64, SRC_EXEC, sreg(sk)); // exec = s[Tk]
+			branch_or_jump(long_join[e], SP_CBRANCH_EXECZ, SP_CBRANCH_EXECNZ, cont_pos(cont[e]));
 		}
-		if (!cb[e].prologue.empty()) {
-			memcpy(&img[area + at], cb[e].prologue.data(), cb[e].prologue.size());
-			at += cb[e].prologue.size();
-		}
-		if (!cb[e].hoist.empty()) {
-			memcpy(&img[area + at], cb[e].hoist.data(), cb[e].hoist.size());
-			at += cb[e].hoist.size();
-		}
+		append(cb[e].prologue.data(), cb[e].prologue.size());
+		append(cb[e].hoist.data(), cb[e].hoist.size());
 		for (int r = 0; r < 6; r++) {
 			if (!(pre_mask[e] & (1u << r)))
 				continue;
@@ -574,19 +557,16 @@ asm_jit_emit(const dprog_host &xl, int mode, const std::vector<dp_map> &table,
 				v = nx < n && placed[nx] ? code_off(nx) : 0;
 			}
 			uint32_t ic;
-			if (r != 2 && inline_code(v, &ic)) { // s_mov_b32 s(10+r), <inline constant>
-				put32(at, 0xbe800000u | ((uint32_t)(AH_S_OPND + r) << 16) | ic);
-				at += 4;
+			if (r != 2 && inline_i64((int32_t)v, &ic)) {
+				G.sop1(S1_MOV_B32, AH_S_OPND + r, opnd{ic});
 				continue;
 			}
-			copy_t(at, AH_JT_MOV_S10 + r, 8);
-			put32(at + 4, v);
-			at += 8;
+			put32(copy_t(AH_JT_MOV_S10 + r, 8) + 4, v);
 		}
 		if (cb[e].fast && cb[e].splice_h >= 0) {
 			// the fast body, the interpreter's handler body as its slow path, the rest
 			const cc_block &c = cb[e];
-			const uint32_t sh = (uint32_t)c.splice_h, sl = splice_len(e);
+			const uint32_t sl = splice_len(e);
 			std::vector<uint8_t> b(c.body);
 			for (uint32_t at_br : c.splice_br) {
 				if (at_br == ~0u)
@@ -598,144 +578,86 @@ asm_jit_emit(const dprog_host &xl, int mode, const std::vector<dp_map> &table,
 				b[at_br] = (uint8_t)rel;
 				b[at_br + 1] = (uint8_t)(rel >> 8);
 			}
-			memcpy(&img[area + at], b.data(), c.splice_at);
-			at += c.splice_at;
-			for (int r = 0; r < 2; r++) { // s_mov_b32 s(10 + r), literal
-				put32(at, 0xbe8000ffu | ((uint32_t)(AH_S_OPND + r) << 16));
-				put32(at + 4, c.splice_sval[r]);
-				at += 8;
-			}
-			at += copy_body(at, sh);
-			put32(at, 0xbf8cc07fu); // s_waitcnt lgkmcnt(0)
-			at += 4;
-			memcpy(&img[area + at], b.data() + c.splice_at, b.size() - c.splice_at);
-			at += b.size() - c.splice_at;
+			append(b.data(), c.splice_at);
+			for (int r = 0; r < 2; r++)
+				G.sop1(S1_MOV_B32, AH_S_OPND + r, opnd{SRC_LIT, c.splice_sval[r]});
+			copy_body((uint32_t)c.splice_h);
+			G.wait_lgkm();
+			append(b.data() + c.splice_at, b.size() - c.splice_at);
 		} else if (cb[e].fast) {
-			if (!cb[e].body.empty())
-				memcpy(&img[area + at], cb[e].body.data(), cb[e].body.size());
-			at += cb[e].body.size();
+			append(cb[e].body.data(), cb[e].body.size());
 		} else {
-			at += copy_body(at, h);
-			if (ah_flags[h] & 2) {
-				copy_t(at, AH_JT_WAIT, 4);
-				at += 4;
-			}
+			copy_body(h);
+			if (ah_flags[h] & 2)
+				copy_t(AH_JT_WAIT, 4);
 		}
 		if (structured && (ah_flags[h] & 1) && cb[e].sdir == 0) {
 			// decided at compile time, never taken: the taken block's join finds no lane
-			const uint32_t sk = AH_S_JOIN + 2 * (uint32_t)jdepth[e];
-			put32(at, 0xbe800000u | (sk << 16) | (0x01u << 8) | 128u); // s_mov_b64 s[Tk], 0
-			at += 4;
+			G.sop1(S1_MOV_B64, AH_S_JOIN + 2 * jdepth[e], opnd{128}); // s[Tk] = 0
 		} else if (structured && (ah_flags[h] & 1)) {
-			// s_and_b64 s[Tk], vcc, exec; s_andn2_b64 exec, exec, vcc; s_cbranch_execz join
-			const uint32_t sk = AH_S_JOIN + 2 * (uint32_t)jdepth[e];
-			put32(at, 0x80000000u | (0x0du << 23) | (sk << 16) | (126u << 8) | 106u);
-			put32(at + 4, 0x80000000u | (0x13u << 23) | (126u << 16) | (106u << 8) | 126u);
-			at += 8;
-			const uint32_t tk = xl.entries[e].target;
-			if (!long_cond[e]) {
-				sopp(at, OP_EXECZ, pos[tk]);
-				at += 4;
-			} else {
-				put32(at, 0xbf800000u | (OP_EXECNZ << 16) | (LJ / 4));
-				long_jump(at + 4, pos[tk]);
-				at += 4 + LJ;
-			}
+			// s[Tk] = the taken lanes, which wait; the others go on (or, none left, the join)
+			const int sk = AH_S_JOIN + 2 * jdepth[e];
+			G.sop2(S2_AND_B64, sk, opnd{SRC_VCC}, opnd{SRC_EXEC});
+			G.sop2(S2_ANDN2_B64, SRC_EXEC, opnd{SRC_EXEC}, opnd{SRC_VCC});
+			branch_or_jump(long_cond[e], SP_CBRANCH_EXECZ, SP_CBRANCH_EXECNZ, pos[xl.entries[e].target]);
 		} else if ((ah_flags[h] & 1) && cb[e].sdir == 1) { // statically taken by every lane
 			const uint32_t tk = xl.entries[e].target;
-			if (!long_cond[e]) {
-				copy_t(at, AH_JT_BR, 4);
-				patch_simm16(at, pos[tk]);
-				at += 4;
-			} else {
-				copy_t(at, AH_JT_JL, jl_len);
-				put32(at + 4, code_off(tk));
-				at += jl_len;
-			}
+			if (!long_cond[e])
+				patch_simm16(copy_t(AH_JT_BR, 4), pos[tk]);
+			else
+				put32(copy_t(AH_JT_JL, jl_len) + 4, code_off(tk));
 		} else if ((ah_flags[h] & 1) && cb[e].sdir < 0 && rev_cond[e]) {
-			// s_and_b64 s[48:49], vcc, exec          (lanes that loop)
-			// s_andn2_b64 s[18:19], exec, vcc        (lanes that leave; SCC = any)
-			// s_cbranch_scc0 .Lloop
-			// s_mov_b64 exec, s[18:19]
-			// v_mov_b32 v41, <code offset of the fall-through block>   (park them there)
-			// s_mov_b64 exec, s[48:49]
-			// s_cbranch_execnz .Lloop
-			// (long jump to .Lr_schedule)
-			// .Lloop: s_branch <taken block> (or a long jump)
+			// the lanes that loop go on; the lanes that leave park at the fall-through block; when
+			// none loops any more the scheduler takes over
 			const uint32_t tk = xl.entries[e].target, nx = xl.entries[e].next;
-			const size_t loop_at = at + RC;
+			const size_t loop_at = g.size() + RC; // .Lloop: the jump to the taken block
 			// (both branches go to the taken block itself when it is in reach, not through .Lloop)
-			auto to_loop = [&](size_t a) -> uint32_t {
-				return !long_cond[e] && fits_simm16((int64_t)pos[tk] - (int64_t)(a + 4)) ? pos[tk]
-													 : (uint32_t)loop_at;
+			auto to_loop = [&]() -> uint32_t {
+				const size_t a = pos[e] + g.size();
+				return !long_cond[e] && fits_simm16((int64_t)pos[tk] - (int64_t)(a + 4))
+					   ? pos[tk] : (uint32_t)(pos[e] + loop_at);
 			};
-			put32(at, 0x80000000u | (0x0du << 23) | (S_MASK << 16) | (126u << 8) | 106u);
-			put32(at + 4, 0x80000000u | (0x13u << 23) | (S_SAVE << 16) | (106u << 8) | 126u);
-			sopp(at + 8, OP_SCC0, to_loop(at + 8));
-			put32(at + 12, 0xbe800000u | (126u << 16) | (0x01u << 8) | S_SAVE);
-			put32(at + 16, 0x7e000000u | ((uint32_t)AH_V_T << 17) | (0x01u << 9) | 255u);
-			put32(at + 20, code_off(nx));
-			put32(at + 24, 0xbe800000u | (126u << 16) | (0x01u << 8) | S_MASK);
-			sopp(at + 28, OP_EXECNZ, to_loop(at + 28));
-			put32(at + 32, 0x80000000u | (S_JUNK << 16) | (255u << 8) | S_CB);
-			put32(at + 36, T[AH_JT_SCHEDULE]);
-			put32(at + 40, 0x80000000u | (0x04u << 23) | ((S_JUNK + 1) << 16) | (128u << 8) | (S_CB + 1));
-			put32(at + 44, 0xbe800000u | (0x1du << 8) | S_JUNK);
-			at = loop_at;
-			if (!long_cond[e]) {
-				sopp(at, OP_BRANCH, pos[tk]);
-				at += 4;
-			} else {
-				long_jump(at, pos[tk]);
-				at += LJ;
-			}
+			G.sop2(S2_AND_B64, AH_S_MASK, opnd{SRC_VCC}, opnd{SRC_EXEC});    // lanes that loop
+			G.sop2(S2_ANDN2_B64, AH_S_SAVE, opnd{SRC_EXEC}, opnd{SRC_VCC});  // lanes that leave; SCC = any
+			branch(SP_CBRANCH_SCC0, to_loop());
+			G.sop1(S1_MOV_B64, SRC_EXEC, sreg(AH_S_SAVE));
+			G.vop1(V1_MOV_B32, AH_V_T, opnd{SRC_LIT, code_off(nx)});         // park them there
+			G.sop1(S1_MOV_B64, SRC_EXEC, sreg(AH_S_MASK));
+			branch(SP_CBRANCH_EXECNZ, to_loop());
+			G.long_jump(T[AH_JT_SCHEDULE]);
+			jump(long_cond[e], pos[tk]);
 		} else if ((ah_flags[h] & 1) && cb[e].sdir < 0) {
 			const uint32_t tk = xl.entries[e].target;
 			if (!long_cond[e]) {
-				copy_t(at, AH_JT_CS, cs_len);
+				const size_t at = copy_t(AH_JT_CS, cs_len);
 				patch_simm16(at + (T[AH_JT_CS_BR] - T[AH_JT_CS]), pos[tk]);
 				put32(at + (T[AH_JT_CS_VT] - T[AH_JT_CS]) + 4, code_off(tk));
-				at += cs_len;
 			} else {
-				copy_t(at, AH_JT_CL, cl_len);
+				const size_t at = copy_t(AH_JT_CL, cl_len);
 				put32(at + (T[AH_JT_CL_LIT] - T[AH_JT_CL]) + 4, code_off(tk));
 				put32(at + (T[AH_JT_CL_VT] - T[AH_JT_CL]) + 4, code_off(tk));
-				at += cl_len;
 			}
 		}
 		if (needs_branch(e)) {
 			const uint32_t sx = succ(e);
-			if (!long_br[e]) {
-				copy_t(at, AH_JT_BR, 4);
-				patch_simm16(at, pos[sx]);
-				at += 4;
-			} else {
-				copy_t(at, AH_JT_JL, jl_len);
-				put32(at + 4, code_off(sx));
-				at += jl_len;
-			}
+			if (!long_br[e])
+				patch_simm16(copy_t(AH_JT_BR, 4), pos[sx]);
+			else
+				put32(copy_t(AH_JT_JL, jl_len) + 4, code_off(sx));
 		}
-		if (leaf_jumps(e)) {
-			if (!long_leaf[e]) {
-				sopp(at, OP_BRANCH, cont_pos(cont[e]));
-				at += 4;
-			} else {
-				long_jump(at, cont_pos(cont[e]));
-				at += LJ;
-			}
-		}
+		if (leaf_jumps(e))
+			jump(long_leaf[e], cont_pos(cont[e]));
 		uint32_t pre, be;
-		if (at != pos[e] + block_size(e, &pre, &be)) {
+		if (g.size() != block_size(e, &pre, &be)) {
 			*err = "internal error: compiled block size mismatch";
 			return EINVAL;
 		}
+		memcpy(&img[area + pos[e]], g.data(), g.size());
 	}
 	if (structured) { // group end: every path has exited
-		const size_t a = end_pos;
-		put32(a, 0x80000000u | (S_JUNK << 16) | (255u << 8) | S_CB);
-		put32(a + 4, T[AH_JT_GROUP_DONE]);
-		put32(a + 8, 0x80000000u | (0x04u << 23) | ((S_JUNK + 1) << 16) | (128u << 8) | (S_CB + 1));
-		put32(a + 12, 0xbe800000u | (0x1du << 8) | S_JUNK);
+		g.clear();
+		G.long_jump(T[AH_JT_GROUP_DONE]);
+		memcpy(&img[area + end_pos], g.data(), g.size());
 	}
 	if (code)
 		code->assign(img.begin() + area, img.begin() + area + total);

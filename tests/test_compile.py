@@ -19,20 +19,6 @@ def _decode(code):
     return r.stdout, r.stderr
 
 
-def _encodings(code):
-    """Re-encode the disassembly: llvm-mc's encoding of every decoded instruction, concatenated
-    (must reproduce `code` exactly when every instruction decodes as what was encoded)."""
-    hexs = " ".join("0x%02x" % b for b in code)
-    r = subprocess.run([LLVM_MC, "--disassemble", "-show-encoding", "-triple=amdgcn-amd-amdhsa",
-                        "-mcpu=gfx950"], input=hexs, capture_output=True, text=True, timeout=60)
-    out = bytearray()
-    for ln in r.stdout.splitlines():
-        if "encoding: [" in ln:
-            enc = ln.split("encoding: [")[1].split("]")[0]
-            out += bytes(int(x, 16) for x in enc.split(","))
-    return bytes(out), r.stdout
-
-
 def _progs(native, env):
     from generic_ebpf_amd import workloads
     out = []
@@ -285,7 +271,7 @@ def test_device_code_layouts(native, env):
 
 def test_no_vop3_reads_two_sgprs(native, env):
     """gfx950's VOP3 reads at most one SGPR; the encoder counts violations and the build fails
-    on one (asm_cc.cpp enc::vop3).  Array maps whose value size is no inline constant (> 64)
+    on one (gfx950_enc.h enc::vop3).  Array maps whose value size is no inline constant (> 64)
     were the round-5 case: the compiled lookup (map base pair + value size) and LDS loads (LDS
     base + value size).  Both layouts compile, and the value size goes through a VGPR."""
     import stdprogs
@@ -308,6 +294,25 @@ def test_no_vop3_reads_two_sgprs(native, env):
         finally:
             p.destroy()
             m.destroy()
+
+
+def test_device_code_digest_repeats():
+    """tools/device_code_digest.py (the byte-identity check of a change to the compiler) gives
+    the same lines in two processes: map handles, which differ between them, are normalised
+    away.  A slice of its corpus: the workloads and 10 random programs in their three forms."""
+    import sys
+    from generic_ebpf_amd import workloads
+    tool = os.path.join(os.path.dirname(__file__), "..", "tools", "device_code_digest.py")
+    cmd = [sys.executable, tool, "--groups", "workloads,random", "--seeds", "10"]
+    procs = [subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+             for _ in range(2)]
+    (a, aerr), (b, berr) = (p.communicate(timeout=300) for p in procs)
+    assert procs[0].returncode == 0 and procs[1].returncode == 0, (aerr[-400:], berr[-400:])
+    assert a == b
+    lines = a.splitlines()
+    # (every program under the 17 knob settings, in both layouts)
+    assert len(lines) == (len(workloads.CONFIGS) + 3 * 10) * 17 * 2
+    assert not any(" error " in ln for ln in lines), [ln for ln in lines if " error " in ln][:3]
 
 
 def test_write_phasing_code(tmp_path):
