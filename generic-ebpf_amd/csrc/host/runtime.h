@@ -1,5 +1,5 @@
 // runtime.h — what the files of the GPU backend share: gpu_runtime.cpp (programs, the launch),
-// stream_scratch.cpp, map_mirror.cpp, map_write_log.cpp, batch.cpp, steer.cpp, and the launchers
+// stream_scratch.cpp, map_mirror.cpp, map_write_log.cpp, batch.cpp, steer.cpp, gather.cpp, and the launchers
 // they call.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -95,6 +95,8 @@ int launch(struct ebpf_prog *ep, dprog_device *dp, const dp_launch &L0, hipStrea
 	   hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, bool hist_overwrite = false,
 	   upd_plan *plan = nullptr);
 int validate_batch(const struct ebpf_pkt_batch *b, uint32_t allowed_flags = 0);
+// steer.cpp: ENODEV for a device index that names no GPU (steer.cpp, gather.cpp)
+int check_device(int device);
 
 hipError_t launch_interp_v0(const dp_launch &L, hipStream_t stream); // interp_v0.hip
 // asm_runtime.cpp

@@ -16,14 +16,6 @@ steer_args(const uint64_t *ret, uint64_t count, const uint32_t *index, const uin
 	return 0;
 }
 
-int
-check_device(int device)
-{
-	if (device < 0 || device >= device_count())
-		return fail(ENODEV, "no such GPU device");
-	return 0;
-}
-
 inline uint32_t
 class_of(const uint64_t *ret, const uint8_t *faults, uint64_t i)
 {
@@ -33,6 +25,14 @@ class_of(const uint64_t *ret, const uint8_t *faults, uint64_t i)
 }
 
 } // namespace
+
+int
+check_device(int device)
+{
+	if (device < 0 || device >= device_count())
+		return fail(ENODEV, "no such GPU device");
+	return 0;
+}
 
 // A counting sort: the reference for the device kernels.
 EBPF_EXPORT int

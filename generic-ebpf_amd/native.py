@@ -127,6 +127,8 @@ FUNCS = {
     "ebpf_batch_steer": (_I, [_VP, _VP, _U64, _VP, _VP]),
     "ebpf_batch_steer_dev": (_I, [_I, _VP, _VP, _U64, _VP, _VP, _VP]),
     "ebpf_batch_select_dev": (_I, [_I, _VP, _VP, _U64, _VP, _VP]),
+    "ebpf_batch_gather": (_I, [_VP, _VP, _U64, _U32, _VP, _U64, _VP]),
+    "ebpf_batch_gather_dev": (_I, [_I, _VP, _VP, _U64, _U32, _VP, _U64, _VP, _VP]),
 }
 DATA_SYMBOLS = ["emt_array", "emt_percpu_array", "emt_hashtable", "emt_percpu_hashtable",
                 "eht_map_lookup_elem", "eht_map_update_elem", "eht_map_delete_elem"]
@@ -561,6 +563,52 @@ def select_dev(device, data_ptr, count, stride, index_ptr, n, extents_ptr, offse
     b = PktBatch(data_ptr, offsets_ptr, count, stride, BATCH_EXTENTS if extents else 0)
     _check(lib().ebpf_batch_select_dev(device, ctypes.byref(b), index_ptr, n, extents_ptr,
                                        stream), "ebpf_batch_select_dev")
+
+
+def gather(data, count, index, out_stride=0, stride=0, offsets=None, extents=False,
+           out_bytes=None):
+    """ebpf_batch_gather on host arrays: packets ``index`` of the batch (data, count, stride,
+    offsets, extents) as run_batch takes it.  Strided form (``out_stride`` > 0): returns
+    (out u8[len(index) * out_stride], None, 0).  Packed form (``out_stride`` 0): returns
+    (out u8[out_bytes], out_offsets u64[len(index) + 1], code) with code 0 or errno.ENOSPC;
+    ``out_bytes`` None sizes the output to fit."""
+    assert data.dtype == np.uint8 and data.flags["C_CONTIGUOUS"]
+    index = np.ascontiguousarray(index, dtype=np.uint32)
+    offs = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
+    b = PktBatch(data.ctypes.data, None if offs is None else offs.ctypes.data, count, stride,
+                 BATCH_EXTENTS if extents else 0)
+    n = len(index)
+    f = lib().ebpf_batch_gather
+    if out_stride:
+        out = np.zeros(n * out_stride, dtype=np.uint8)
+        _check(f(ctypes.byref(b), index.ctypes.data, n, out_stride, out.ctypes.data, out.nbytes,
+                 None), "ebpf_batch_gather")
+        return out, None, 0
+    out_offsets = np.zeros(n + 1, dtype=np.uint64)
+    if out_bytes is None:   # (snprintf's rule: a first call with no room says how much is needed)
+        code = f(ctypes.byref(b), index.ctypes.data, n, 0, np.zeros(1, dtype=np.uint8).ctypes.data,
+                 0, out_offsets.ctypes.data)
+        if code not in (0, errno.ENOSPC):
+            raise EbpfError(code, "ebpf_batch_gather")
+        out_bytes = int(out_offsets[n])
+    out = np.zeros(max(out_bytes, 1), dtype=np.uint8)
+    code = f(ctypes.byref(b), index.ctypes.data, n, 0, out.ctypes.data, out_bytes,
+             out_offsets.ctypes.data)
+    if code not in (0, errno.ENOSPC):
+        raise EbpfError(code, "ebpf_batch_gather")
+    return out[:out_bytes], out_offsets, code
+
+
+def gather_dev(device, data_ptr, count, stride, index_ptr, n, out_stride, out_ptr, out_bytes,
+               out_offsets_ptr=None, offsets_ptr=None, stream=None, extents=False):
+    """ebpf_batch_gather_dev: packets index[0..n) of the batch (data_ptr, count, stride,
+    offsets_ptr, extents) as run_batch_dev takes it, copied to ``out_ptr``: slots of
+    ``out_stride`` bytes, or (``out_stride`` 0) packed, with their n + 1 offsets written to
+    ``out_offsets_ptr``; device pointers (ints); asynchronous on ``stream``."""
+    b = PktBatch(data_ptr, offsets_ptr, count, stride, BATCH_EXTENTS if extents else 0)
+    _check(lib().ebpf_batch_gather_dev(device, ctypes.byref(b), index_ptr, n, out_stride, out_ptr,
+                                       out_bytes, out_offsets_ptr, stream),
+           "ebpf_batch_gather_dev")
 
 
 def set_variant(v):

@@ -334,6 +334,60 @@ int ebpf_batch_steer_dev(int device, const uint64_t *ret_dev, const uint8_t *fau
 int ebpf_batch_select_dev(int device, const struct ebpf_pkt_batch *batch, const uint32_t *index_dev,
 			  uint64_t n, uint64_t *extents_dev, void *stream);
 
+/* Gathering packets into a dense batch: a list of n packets of `batch` (a class of a steered
+ * batch, the whole steering index, any list of the caller's own: duplicates and any order are
+ * fine) copied, in list order, into `out`.  A class can then leave the device on its own (a TX
+ * ring, one copy to the host), and a second-stage program gets a dense batch:
+ *
+ *   ebpf_batch_gather_dev(dev, &batch, index + starts[b], k, 64, out, k * 64, NULL, s);
+ *   sub = {out, NULL, k, 64, 0};             (16-byte-aligned out: the staged kernel)
+ *   ebpf_prog_run_batch_dev(ep2, dev, &sub, ret2, faults2, hist2, s);
+ *
+ * Packet index[j] has the (start, end) that ebpf_batch_select_dev would write for it, whatever
+ * form `batch` has; its length len_j is end - start, or 0 when end < start or end - start >= 2^32
+ * (the run functions' rule), and 0 for an index >= batch->count.  All offsets are 64-bit: packets
+ * may lie 4 GiB or more from batch->data and the output may exceed 4 GiB.
+ *
+ * Strided form (out_stride > 0; out_offsets must be NULL): slot j is bytes [j * out_stride,
+ *   (j + 1) * out_stride) of out and holds the packet's first min(len_j, out_stride) bytes, then
+ *   zero bytes up to the slot's end (out_stride below the length snaps the packet, as a capture's
+ *   snaplen does).  Needs n * out_stride <= out_bytes.  {out, NULL, n, out_stride, 0} is then a
+ *   batch; with out_stride 64 and out 16-byte aligned it takes the staged kernel.
+ * Packed form (out_stride == 0; out_offsets has n + 1 entries): out_offsets[0] = 0,
+ *   out_offsets[j + 1] = out_offsets[j] + len_j, and packet j's bytes lie at out + out_offsets[j]:
+ *   a tight pack, every length kept exactly, so a second stage faults on exactly the same loads.
+ *   {out, out_offsets, n, 0, 0} is then an offsets-form batch.  out_offsets is always written in
+ *   full, and no byte at or past out + out_bytes is written: out_offsets[n] is the size needed and
+ *   the output is complete iff out_offsets[n] <= out_bytes (snprintf's rule).
+ * Both: only bytes of [out, out + n * out_stride), or of [out, out + min(out_offsets[n],
+ * out_bytes)), are written; out may have any alignment; out overlapping batch->data is undefined.
+ * Only the listed packets' bytes, index[0 .. n) and the listed packets' offsets entries are read; a
+ * listed packet of length 0 reads no data.  The output is a function of the inputs alone.  Gathering
+ * a whole steering index with n = count reorders the batch by class in one call: class b then lies
+ * at out + starts[b] * out_stride, or at out_offsets[starts[b] .. starts[b+1]].
+ *
+ * ebpf_batch_gather: host buffers; no GPU needed (the statement of what the device function
+ *   computes).  Packed form: ENOSPC when out_offsets[n] > out_bytes, with out_offsets and the
+ *   bytes that fit written.
+ * ebpf_batch_gather_dev: batch->data, batch->offsets, index_dev, out_dev and out_offsets_dev are
+ *   device memory on `device`; enqueued on `stream` (hipStream_t, NULL = default stream), returns
+ *   without synchronising, so the packed form always returns 0 and the caller compares
+ *   out_offsets_dev[n] with out_bytes after the stream.  A fixed-stride batch gathered at its own
+ *   stride, a multiple of 16, with data and out 16-byte aligned, moves 16 bytes a lane; everything
+ *   else goes through a general copy with the same results.  The packed form's temporary storage
+ *   is the library's, per stream, shared with ebpf_batch_steer_dev (8 bytes per 4,096 entries).
+ * Both return 0; EINVAL (a batch that the run functions would refuse; a NULL index or out with
+ * n > 0; out_offsets given with out_stride > 0, or NULL with out_stride == 0; n * out_stride >
+ * out_bytes); E2BIG for n > 0xffffffff.  n == 0 succeeds (the packed form writes out_offsets[0]
+ * = 0).  The device function then returns ENODEV (no GPU, or no such device), ENOMEM (no scratch)
+ * or EIO.  Neither changes the calling thread's current HIP device. */
+int ebpf_batch_gather(const struct ebpf_pkt_batch *batch, const uint32_t *index, uint64_t n,
+		      uint32_t out_stride, void *out, uint64_t out_bytes, uint64_t *out_offsets);
+int ebpf_batch_gather_dev(int device, const struct ebpf_pkt_batch *batch,
+			  const uint32_t *index_dev, uint64_t n, uint32_t out_stride,
+			  void *out_dev, uint64_t out_bytes, uint64_t *out_offsets_dev,
+			  void *stream);
+
 /* Select the device used by ebpf_prog_run_batch for the calling thread. */
 int ebpf_gpu_set_device(int device);
 
