@@ -49,12 +49,12 @@ enum dp_kind : uint16_t {
 	// Stores into map values with the device batch's counter semantics (ebpf_gpu.h "Stores into
 	// map values"): the STX of a counter update — the translator found LDX{W,DW} X = [P + off];
 	// ADD/SUB X; STX [P + off] = X on one path — stores X like the STX (dst = P, src = X, off;
-	// aux = 4 or 8 bytes) and, into a map value, adds X minus the value it re-reads there
-	// (the packet's own view: nothing stored in between) instead of overwriting it.  aux bit 9:
-	// the update's addend is an immediate, in imm (what the ADD / SUB adds)
+	// aux & DP_AUX_SIZE = 4 or 8 bytes) and, into a map value, adds X minus the value it re-reads
+	// there (the packet's own view: nothing stored in between) instead of overwriting it.
+	// DP_AUX_IMM: the update's addend is an immediate, in imm (what the ADD / SUB adds)
 	DK_CNT_STORE = 0x111,
 	// XADD (standard semantics, BPF_STX | BPF_XADD): *(u32 / u64 *)(dst + off) += src; aux = 4
-	// or 8 bytes, | 0x100 when imm was BPF_FETCH (src = the old value)
+	// or 8 bytes (DP_AUX_SIZE), | DP_AUX_FETCH when imm was BPF_FETCH (src = the old value)
 	DK_XADD = 0x112,
 	// A program that reads its own stores into map values, or whose writes are capped, starts
 	// here: the lane's overlay is emptied and its write count zeroed (DP_OVL_COUNT, DP_WCOUNT = 0)
@@ -86,6 +86,15 @@ enum dp_kind : uint16_t {
 // kernel (16 result slots)
 #define DP_WPHASE_PERIOD_SHIFT 16u
 #define DP_WPHASE_WIDE 0x80000000u
+// dp_entry.aux sub-fields (besides a fault code or a map's table index)
+#define DP_AUX_SIZE 0xffu   // DK_CNT_STORE, DK_XADD: the access's bytes (4 or 8)
+#define DP_AUX_FETCH 0x100u // DK_XADD: BPF_FETCH, src receives the old value
+#define DP_AUX_IMM 0x200u   // DK_CNT_STORE: the addend is an immediate, in imm
+// ... and two marks that only the translator reads:
+#define DP_AUX_SYNTH 1u     // an ADD64 dst, 0 the translator made (MOD by a zero immediate, a
+                            // conditional jump of offset 0): not an ADD of the program's, so no
+                            // counter update and no loop decrement
+#define DP_AUX_DELETE 1u    // DK_CALL_UPDATE before its map is resolved: map_delete_elem
 #define DP_LOOP_BUDGET (1u << 20) // taken backward jumps a lane may make (standard semantics)
 #define DP_CLS_JMP32 6
 
@@ -98,7 +107,7 @@ struct dp_entry {
 	uint16_t kind;    // dp_kind or opcode
 	uint8_t dst, src;
 	int16_t off;
-	uint16_t aux;     // DK_FAULT: fault code
+	uint16_t aux;     // DK_FAULT: fault code; a map helper: the map's table index; DP_AUX_*
 };
 static_assert(sizeof(dp_entry) == 32, "dp_entry is 32 bytes");
 

@@ -547,7 +547,7 @@ ebpf_interp_v0(dp_launch L)
 		}
 		if (k == DK_CNT_STORE || k == DK_XADD || cls == 0x2 || cls == 0x3) {
 			// ST / STX; the STX of a counter update; XADD (standard semantics)
-			const uint32_t size = k >= 0x100 ? (e.aux & 0xff)
+			const uint32_t size = k >= 0x100 ? (e.aux & DP_AUX_SIZE)
 					      : (k & 0x18) == 0x00 ? 4 : (k & 0x18) == 0x08 ? 2 : (k & 0x18) == 0x10 ? 1 : 8;
 			const uint64_t a = R[e.dst][tid] + (uint64_t)(int64_t)e.off;
 			int mi;
@@ -575,7 +575,7 @@ ebpf_interp_v0(dp_launch L)
 				active = false;
 				continue;
 			}
-			if (k == DK_XADD && (e.aux & 0x100)) // BPF_FETCH: src = the old value
+			if (k == DK_XADD && (e.aux & DP_AUX_FETCH)) // BPF_FETCH: src = the old value
 				R[e.src][tid] = old & mask;
 			continue;
 		}

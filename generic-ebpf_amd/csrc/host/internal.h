@@ -167,9 +167,10 @@ struct dprog_device {
 struct dprog_host;
 bool prog_writes_maps(const dprog_host &xl);
 
-// Abstract value of a register (pointer provenance), computed by translate.cpp's dataflow pass
-// over the state tree.  Used to specialise device handlers: packet loads at known offsets come
-// from registers, stack accesses at known offsets from LDS, map lookups resolve statically.
+// Abstract value of a register (pointer provenance), computed by the translator's dataflow pass
+// (xlate_dataflow.cpp) over the state tree.  Used to specialise device handlers: packet loads at
+// known offsets come from registers, stack accesses at known offsets from LDS, map lookups
+// resolve statically.
 enum av_kind : uint8_t {
 	AV_UNKNOWN = 0,
 	AV_CONST,       // off = the 64-bit value
@@ -229,7 +230,7 @@ struct dprog_host {
 	bool write_cap = false;              // a path may log more than DP_WRITES_MAX writes (loops):
 	                                     // the device counts them per packet (DP_VF_WCAP)
 	bool reads_counters = false;         // loops, and a live counter-idiom register or XADD with
-	                                     // BPF_FETCH on the slot graph (translate.cpp
+	                                     // BPF_FETCH on the slot graph (xlate_slots.cpp
 	                                     // slot_reads_counters): the overlay holds the packet's
 	                                     // view, DP_OVL_MAX words, the next faults WRITES
 	int error = 0;
@@ -255,7 +256,7 @@ void env_acquire(struct ebpf_env *ee);
 void env_release(struct ebpf_env *ee);
 void obj_init(struct ebpf_env *ee, struct ebpf_obj *eo);
 
-// translate.cpp
+// translate.cpp (its passes: xlate.h, xlate_*.cpp)
 int translate_program(struct ebpf_prog *ep, dprog_host &out);
 
 // gpu_runtime.cpp (the GPU backend's own interfaces: runtime.h)

@@ -277,7 +277,7 @@ def test_loop_back_edge_code_shape(native, env):
 
 
 def test_counted_loop_needs_no_count(native, env):
-    """translate.cpp elide_loop_count: a single counted loop whose counter enters in [1, K] with
+    """xlate_loops.cpp elide_loop_count: a single counted loop whose counter enters in [1, K] with
     K - 1 <= 2^20 drops its per-lane count (C3L: IHL in [5, 12]; countdown(n) for n <= 2^20 + 1,
     which takes exactly the budget); one more trip than the budget keeps it (the GPU budget test
     then faults LOOP), and so do programs with two loops."""
