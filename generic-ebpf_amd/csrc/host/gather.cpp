@@ -29,28 +29,6 @@ gather_args(const struct ebpf_pkt_batch *batch, const uint32_t *index, uint64_t 
 	return 0;
 }
 
-// Packet i's start and its length: the run functions' rule (0 for an end below the start or 2^32
-// bytes or more past it) and 0 for an index past the batch.
-inline uint32_t
-span_of(const struct ebpf_pkt_batch &b, uint32_t i, uint64_t *start)
-{
-	uint64_t s = 0, e = 0;
-	if (i < b.count) {
-		if (b.offsets == nullptr) {
-			s = (uint64_t)i * b.stride;
-			e = s + b.stride;
-		} else if (b.flags & EBPF_BATCH_EXTENTS) {
-			s = b.offsets[2 * (uint64_t)i];
-			e = b.offsets[2 * (uint64_t)i + 1];
-		} else {
-			s = b.offsets[i];
-			e = b.offsets[(uint64_t)i + 1];
-		}
-	}
-	*start = s;
-	return (e < s || e - s > 0xffffffffull) ? 0u : (uint32_t)(e - s);
-}
-
 } // namespace
 
 EBPF_EXPORT int
@@ -65,7 +43,7 @@ ebpf_batch_gather(const struct ebpf_pkt_batch *batch, const uint32_t *index, uin
 	if (out_stride != 0) {
 		for (uint64_t j = 0; j < n; j++) {
 			uint64_t s;
-			const uint32_t len = std::min(span_of(*batch, index[j], &s), out_stride);
+			const uint32_t len = std::min(packet_span(*batch, index[j], &s), out_stride);
 			uint8_t *slot = o + j * out_stride;
 			if (len != 0)
 				memcpy(slot, data + s, len);
@@ -76,7 +54,7 @@ ebpf_batch_gather(const struct ebpf_pkt_batch *batch, const uint32_t *index, uin
 	uint64_t at = 0;
 	for (uint64_t j = 0; j < n; j++) {
 		uint64_t s;
-		const uint32_t len = span_of(*batch, index[j], &s);
+		const uint32_t len = packet_span(*batch, index[j], &s);
 		out_offsets[j] = at;
 		const uint64_t room = at < out_bytes ? out_bytes - at : 0;
 		if (len != 0 && room != 0)

@@ -4,7 +4,29 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-struct ebpf_pkt_batch;
+#include "ebpf_gpu.h"
+
+// Packet i's start and its length on the host (gather.cpp, scatter.cpp): the run functions' rule
+// (0 for an end below the start or 2^32 bytes or more past it) and 0 for an index past the batch.
+inline uint32_t
+packet_span(const struct ebpf_pkt_batch &b, uint32_t i, uint64_t *start)
+{
+	uint64_t s = 0, e = 0;
+	if (i < b.count) {
+		if (b.offsets == nullptr) {
+			s = (uint64_t)i * b.stride;
+			e = s + b.stride;
+		} else if (b.flags & EBPF_BATCH_EXTENTS) {
+			s = b.offsets[2 * (uint64_t)i];
+			e = b.offsets[2 * (uint64_t)i + 1];
+		} else {
+			s = b.offsets[i];
+			e = b.offsets[(uint64_t)i + 1];
+		}
+	}
+	*start = s;
+	return (e < s || e - s > 0xffffffffull) ? 0u : (uint32_t)(e - s);
+}
 
 // List entries per tile of the packed form's length and offset passes: one workgroup of 256 sums,
 // and later scans, GATHER_TILE consecutive entries.

@@ -90,6 +90,7 @@ ensure_translated(struct ebpf_prog *ep)
 		x->error = err;
 	if (!x->error) {
 		x->asm_needs_general = asm_program_needs_general(*x);
+		x->asm_stores_last = x->asm_needs_general && asm_program_stores_last(*x);
 		x->asm_gstage = asm_program_gstage(*x);
 		x->asm_pktv = asm_program_hdrlds(*x);
 		x->asm_hdrlds = x->asm_pktv && getenv("EBPF_NOHDRLDS") == nullptr;
@@ -274,8 +275,11 @@ launch(struct ebpf_prog *ep, dprog_device *dp, const dp_launch &L0, hipStream_t 
 	// the staged kernel reads its packets with LDS-DMA, 16 bytes a lane: only a 16-byte-aligned
 	// base takes it (ebpf_gpu.h ebpf_prog_run_batch_dev); any other runs the general kernel
 	const bool aligned = (reinterpret_cast<uintptr_t>(L0.data) & 15) == 0;
-	const int mode =
-	    (L0.offsets == nullptr && L0.stride == 64 && aligned && !ep->xlated->asm_needs_general) ? 1 : 0;
+	// a program whose stores may touch the packet reads it from memory (the general kernel), unless
+	// no packet read can follow such a store (asm_program_stores_last): a storing second stage
+	// over a gathered batch
+	const bool staged_ok = !ep->xlated->asm_needs_general || ep->xlated->asm_stores_last;
+	const int mode = (L0.offsets == nullptr && L0.stride == 64 && aligned && staged_ok) ? 1 : 0;
 	int err;
 	// an overlay larger than the lanes keep on chip: the portable interpreter, spilled
 	const bool spill = ep->xlated->vstore_overlay && ep->xlated->ovl_entries > DP_OVL_MAX;

@@ -203,7 +203,8 @@ struct dprog_host {
 	uint32_t start = 0;
 	std::vector<struct ebpf_map *> maps; // referenced array maps, in dp_map table order
 	bool writes_memory = false;          // any reachable ST/STX through a non-r10 base
-	bool asm_needs_general = false;      // a store may touch the packet: no staged mode
+	bool asm_needs_general = false;      // a store may touch the packet: no staged mode, unless ...
+	bool asm_stores_last = false;        // ... nothing that may read the packet follows such a store
 	bool asm_gstage = false;             // general kernels stage packet headers (asm_program_gstage)
 	bool asm_pktv = false;               // packet loads at run-time offsets (LDXPKTV), no packet stores
 	bool asm_hdrlds = false;             // ... and keep them in LDS for run-time-offset loads

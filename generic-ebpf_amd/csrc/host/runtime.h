@@ -107,6 +107,7 @@ hipError_t launch_interp_asm(const dp_launch &L, hipStream_t stream, int device,
 int asm_available(int device);
 bool asm_lds_fits(int mode, uint32_t map_lds_bytes, uint32_t stack_stride);
 bool asm_program_needs_general(const dprog_host &xl);
+bool asm_program_stores_last(const dprog_host &xl);
 bool asm_program_gstage(const dprog_host &xl);
 bool asm_program_hdrlds(const dprog_host &xl);
 bool asm_hdrlds_fits(uint32_t map_lds_bytes, uint32_t stack_stride);

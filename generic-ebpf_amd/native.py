@@ -129,6 +129,10 @@ FUNCS = {
     "ebpf_batch_select_dev": (_I, [_I, _VP, _VP, _U64, _VP, _VP]),
     "ebpf_batch_gather": (_I, [_VP, _VP, _U64, _U32, _VP, _U64, _VP]),
     "ebpf_batch_gather_dev": (_I, [_I, _VP, _VP, _U64, _U32, _VP, _U64, _VP, _VP]),
+    "ebpf_batch_scatter": (_I, [_VP, _VP, _U64, _U32, _VP, _U64, _VP]),
+    "ebpf_batch_scatter_dev": (_I, [_I, _VP, _VP, _U64, _U32, _VP, _U64, _VP, _VP]),
+    "ebpf_batch_merge": (_I, [_VP, _VP, _U64, _VP, _U64, _VP, _VP]),
+    "ebpf_batch_merge_dev": (_I, [_I, _VP, _VP, _U64, _VP, _U64, _VP, _VP, _VP]),
 }
 DATA_SYMBOLS = ["emt_array", "emt_percpu_array", "emt_hashtable", "emt_percpu_hashtable",
                 "eht_map_lookup_elem", "eht_map_update_elem", "eht_map_delete_elem"]
@@ -609,6 +613,62 @@ def gather_dev(device, data_ptr, count, stride, index_ptr, n, out_stride, out_pt
     _check(lib().ebpf_batch_gather_dev(device, ctypes.byref(b), index_ptr, n, out_stride, out_ptr,
                                        out_bytes, out_offsets_ptr, stream),
            "ebpf_batch_gather_dev")
+
+
+def scatter(data, count, index, dense, in_stride=0, stride=0, offsets=None, extents=False,
+            in_offsets=None, in_bytes=None):
+    """ebpf_batch_scatter on host arrays: the slots of ``dense`` (``in_stride`` bytes each, or
+    packed at ``in_offsets``) written back, in place, into packets ``index`` of the batch (data,
+    count, stride, offsets, extents) as run_batch takes it.  ``in_bytes`` None: all of
+    ``dense``."""
+    assert data.dtype == np.uint8 and data.flags["C_CONTIGUOUS"] and data.flags["WRITEABLE"]
+    dense = np.ascontiguousarray(dense, dtype=np.uint8)
+    index = np.ascontiguousarray(index, dtype=np.uint32)
+    offs = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
+    in_offs = None if in_offsets is None else np.ascontiguousarray(in_offsets, dtype=np.uint64)
+    b = PktBatch(data.ctypes.data, None if offs is None else offs.ctypes.data, count, stride,
+                 BATCH_EXTENTS if extents else 0)
+    _check(lib().ebpf_batch_scatter(ctypes.byref(b), index.ctypes.data, len(index), in_stride,
+                                    dense.ctypes.data, len(dense) if in_bytes is None else in_bytes,
+                                    None if in_offs is None else in_offs.ctypes.data),
+           "ebpf_batch_scatter")
+
+
+def scatter_dev(device, data_ptr, count, stride, index_ptr, n, in_stride, in_ptr, in_bytes,
+                in_offsets_ptr=None, offsets_ptr=None, stream=None, extents=False):
+    """ebpf_batch_scatter_dev: the slots at ``in_ptr`` (``in_stride`` bytes each, or
+    (``in_stride`` 0) packed at the n + 1 offsets of ``in_offsets_ptr``) written back into packets
+    index[0..n) of the batch (data_ptr, count, stride, offsets_ptr, extents); device pointers
+    (ints); asynchronous on ``stream``."""
+    b = PktBatch(data_ptr, offsets_ptr, count, stride, BATCH_EXTENTS if extents else 0)
+    _check(lib().ebpf_batch_scatter_dev(device, ctypes.byref(b), index_ptr, n, in_stride, in_ptr,
+                                        in_bytes, in_offsets_ptr, stream),
+           "ebpf_batch_scatter_dev")
+
+
+def merge(ret, faults, index, ret2, faults2=None):
+    """ebpf_batch_merge on host arrays, in place: ret[index[j]] = ret2[j] and (``faults`` given)
+    faults[index[j]] = faults2[j], or 0 without ``faults2``."""
+    assert ret.dtype == np.uint64 and ret.flags["C_CONTIGUOUS"] and ret.flags["WRITEABLE"]
+    assert faults is None or (faults.dtype == np.uint8 and faults.flags["C_CONTIGUOUS"]
+                              and len(faults) == len(ret))
+    index = np.ascontiguousarray(index, dtype=np.uint32)
+    ret2 = np.ascontiguousarray(ret2, dtype=np.uint64)
+    if faults2 is not None:
+        faults2 = np.ascontiguousarray(faults2, dtype=np.uint8)
+        assert len(faults2) == len(index)
+    assert len(ret2) == len(index)
+    _check(lib().ebpf_batch_merge(ret.ctypes.data, None if faults is None else faults.ctypes.data,
+                                  len(ret), index.ctypes.data, len(index), ret2.ctypes.data,
+                                  None if faults2 is None else faults2.ctypes.data),
+           "ebpf_batch_merge")
+
+
+def merge_dev(device, ret_ptr, faults_ptr, count, index_ptr, n, ret2_ptr, faults2_ptr=None,
+              stream=None):
+    """ebpf_batch_merge_dev: device pointers (ints); asynchronous on ``stream``."""
+    _check(lib().ebpf_batch_merge_dev(device, ret_ptr, faults_ptr, count, index_ptr, n, ret2_ptr,
+                                      faults2_ptr, stream), "ebpf_batch_merge_dev")
 
 
 def set_variant(v):

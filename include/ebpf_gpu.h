@@ -388,6 +388,72 @@ int ebpf_batch_gather_dev(int device, const struct ebpf_pkt_batch *batch,
 			  void *out_dev, uint64_t out_bytes, uint64_t *out_offsets_dev,
 			  void *stream);
 
+/* Scattering a dense batch back: the inverse of the gather, and the merge of a second stage's
+ * results.  A second-stage program may store into its packets and returns a verdict of its own;
+ * after a gathered second stage the rewritten bytes lie in the dense copy and ret2 / faults2 are
+ * indexed by list position.  These functions put both back where the batch keeps them, so that the
+ * pipeline ends with one batch and one ret array in packet order:
+ *
+ *   ebpf_batch_gather_dev(dev, &batch, index + starts[b], k, 64, out, k * 64, NULL, s);
+ *   ebpf_prog_run_batch_dev(ep2, dev, &sub, ret2, faults2, NULL, s);      (sub as above)
+ *   ebpf_batch_scatter_dev(dev, &batch, index + starts[b], k, 64, out, k * 64, NULL, s);
+ *   ebpf_batch_merge_dev(dev, ret, faults, batch.count, index + starts[b], k, ret2, faults2, s);
+ *
+ * Scatter writes into batch->data through the const pointer, as the run functions do for a program
+ * that stores into its packets.  Packet index[j] has the (start, len_j) that ebpf_batch_gather
+ * uses, whatever form `batch` has: the length-0 rule for an end below the start or 2^32 or more
+ * past it, and length 0 for an index >= batch->count.
+ *
+ * Strided form (in_stride > 0; in_offsets must be NULL): slot j is in + j * in_stride and k_j =
+ *   min(len_j, in_stride).  Needs n * in_stride <= in_bytes.
+ * Packed form (in_stride == 0; in_offsets has n + 1 entries): slot j is bytes [in_offsets[j],
+ *   in_offsets[j + 1]) of in, read as an offsets-form batch reads them: its length m_j follows the
+ *   same length-0 rule and is then cut so that no byte at or past in + in_bytes is read; k_j =
+ *   min(len_j, m_j).  {in, in_offsets} as a packed gather left them scatter back exactly what was
+ *   gathered, also after a truncated gather (out_offsets[n] > out_bytes).
+ * Both: bytes [start, start + k_j) of batch->data become slot j's first k_j bytes; a packet longer
+ * than its slot keeps its remaining bytes.  No other byte of batch->data is written: not the gaps
+ * between packets, not an unlisted neighbour that shares 16 bytes with a listed packet, not a
+ * packet's bytes past k_j.  Only the slots' first k_j bytes, index[0 .. n), in_offsets[0 .. n] and
+ * the listed packets' offsets entries are read; a slot's padding is never read.  A steering list
+ * names every packet once.  If a packet is listed more than once, or listed packets overlap, every
+ * affected byte ends as the corresponding byte of one of the candidates, which one is unspecified
+ * (the rule for stores into overlapping packets above); where the candidates agree — a
+ * deterministic second stage over a gathered list with duplicates — the result is exact.  `in`
+ * overlapping batch->data is undefined.
+ *
+ * Merge: for j < n with index[j] < count, ret[index[j]] = ret2[j] and, if faults is given,
+ * faults[index[j]] = faults2 ? faults2[j] : 0.  An index >= count writes nothing, and nothing
+ * outside ret[0 .. count) and faults[0 .. count) is written.  Of duplicate listings one's value
+ * lands whole.  The merged histogram is `starts` of a second ebpf_batch_steer_dev over the merged
+ * ret / faults (bin b = starts[b + 1] - starts[b]), which also lists the final classes.
+ *
+ * ebpf_batch_scatter, ebpf_batch_merge: host buffers; no GPU needed (the statement of what the
+ *   device functions compute, and the step for a caller of ebpf_prog_run_batch).
+ * ebpf_batch_scatter_dev, ebpf_batch_merge_dev: every pointer (batch->data, batch->offsets
+ *   included) is device memory on `device`; enqueued on `stream` (hipStream_t, NULL = default
+ *   stream), return without synchronising, need no temporary storage.  A fixed-stride batch
+ *   scattered from its own stride, a multiple of 16, with data and in 16-byte aligned, moves 16
+ *   bytes a lane; everything else goes through a general copy with the same results.
+ * Scatter returns 0; EINVAL (a batch that the run functions would refuse; a NULL index or in with
+ * n > 0; in_offsets given with in_stride > 0, or NULL with in_stride == 0; n * in_stride >
+ * in_bytes); E2BIG for n > 0xffffffff.  Merge returns 0; EINVAL for a NULL ret, ret2 or index
+ * with n > 0; E2BIG for n > 0xffffffff.  n == 0 succeeds.  The device functions then return
+ * ENODEV (no GPU, or no such device) or EIO.  None changes the calling thread's current HIP
+ * device. */
+int ebpf_batch_scatter(const struct ebpf_pkt_batch *batch, const uint32_t *index, uint64_t n,
+		       uint32_t in_stride, const void *in, uint64_t in_bytes,
+		       const uint64_t *in_offsets);
+int ebpf_batch_scatter_dev(int device, const struct ebpf_pkt_batch *batch,
+			   const uint32_t *index_dev, uint64_t n, uint32_t in_stride,
+			   const void *in_dev, uint64_t in_bytes,
+			   const uint64_t *in_offsets_dev, void *stream);
+int ebpf_batch_merge(uint64_t *ret, uint8_t *faults, uint64_t count, const uint32_t *index,
+		     uint64_t n, const uint64_t *ret2, const uint8_t *faults2);
+int ebpf_batch_merge_dev(int device, uint64_t *ret_dev, uint8_t *faults_dev, uint64_t count,
+			 const uint32_t *index_dev, uint64_t n, const uint64_t *ret2_dev,
+			 const uint8_t *faults2_dev, void *stream);
+
 /* Select the device used by ebpf_prog_run_batch for the calling thread. */
 int ebpf_gpu_set_device(int device);
 
