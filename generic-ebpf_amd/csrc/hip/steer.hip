@@ -21,23 +21,18 @@
 #include <hip/hip_runtime.h>
 
 #include "ebpf_gpu.h"
+#include "hip/wave_rank.h"
 #include "host/steer.h"
 
 namespace {
 
+using namespace wave_rank;
+
 constexpr uint32_t BINS = EBPF_HIST_BINS;
-constexpr uint32_t CLASS_BITS = 9;
-constexpr uint32_t THREADS = 256;
-constexpr uint32_t WAVES = THREADS / 64;
-constexpr uint32_t WAVE_SPAN = STEER_TILE / WAVES; // packets of a tile that one wave owns
-constexpr uint32_t CHUNKS = WAVE_SPAN / 64;
-constexpr uint32_t NONE = ~0u;                     // the class of a lane past the batch's end
-static_assert(STEER_TILE % THREADS == 0 && WAVE_SPAN % 64 == 0, "tile shape");
 static_assert(BINS <= (1u << CLASS_BITS) && STEER_SEGS <= THREADS, "scan shape");
 
-// The classes of packets first, first + step, ... (NONE past the batch's end).  Every load is
-// issued before the first is used — a packet past the end reads the last packet instead, so no
-// load sits behind a branch — and the wave then waits for memory once, not once per packet.
+// The classes of packets first, first + step, ... (NONE past the batch's end); the loads as
+// load_verdicts issues them.
 template <bool FAULTS, uint32_t N>
 __device__ __forceinline__ void
 load_classes(const uint64_t *__restrict__ ret, const uint8_t *__restrict__ faults, uint64_t count,
@@ -45,63 +40,12 @@ load_classes(const uint64_t *__restrict__ ret, const uint8_t *__restrict__ fault
 {
 	uint64_t r[N];
 	uint32_t f[N];
-#pragma unroll
-	for (uint32_t k = 0; k < N; k++) {
-		const uint64_t i = first + k * step;
-		const uint64_t at = i < count ? i : count - 1;
-		r[k] = ret[at];
-		f[k] = FAULTS ? faults[at] : 0;
-	}
+	load_verdicts<FAULTS>(ret, faults, count, first, step, r, f);
 #pragma unroll
 	for (uint32_t k = 0; k < N; k++) {
 		const uint32_t c = f[k] ? BINS - 1 : (r[k] < 255 ? (uint32_t)r[k] : 255u);
 		cls[k] = first + k * step < count ? c : NONE;
 	}
-}
-
-__device__ __forceinline__ uint32_t
-below(uint64_t mask)
-{
-	return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
-}
-
-// The bits of the class in which the wave's packets (N a lane) differ: a bit that some packet
-// has set and some packet has clear.  Wave-uniform; 2 ballots a bit, once per tile.
-template <uint32_t N>
-__device__ __forceinline__ uint32_t
-varying_bits(const uint32_t (&cls)[N])
-{
-	uint32_t some = 0, every = NONE;
-#pragma unroll
-	for (uint32_t k = 0; k < N; k++) {
-		some |= cls[k] == NONE ? 0u : cls[k];
-		every &= cls[k]; // (NONE is all ones)
-	}
-	uint32_t vary = 0;
-#pragma unroll
-	for (uint32_t k = 0; k < CLASS_BITS; k++)
-		if (__ballot((some >> k) & 1) != 0 && __ballot(!((every >> k) & 1)) != 0)
-			vary |= 1u << k;
-	return __builtin_amdgcn_readfirstlane(vary);
-}
-
-// The lanes of the wave whose class is this lane's (itself included); lanes of class NONE match
-// nothing and nobody.  One ballot per bit of `vary`, the bits in which the wave's classes may
-// differ: a lane keeps the ballot or its complement according to its own bit.
-__device__ __forceinline__ uint64_t
-match_class(uint32_t cls, uint32_t vary)
-{
-	const uint64_t all = __ballot(cls != NONE);
-	uint64_t m = all;
-#pragma unroll
-	for (uint32_t k = 0; k < CLASS_BITS; k++) {
-		if (!(vary & (1u << k))) // (a scalar test: skipping a bit costs no vector work)
-			continue;
-		const bool bit = (cls >> k) & 1;
-		const uint64_t b = __ballot(bit);
-		m &= bit ? b : ~b;
-	}
-	return cls != NONE ? m : 0;
 }
 
 template <bool FAULTS>
@@ -317,19 +261,15 @@ steer_scratch_words(uint64_t count)
 	return (size_t)(ntiles + (ntiles > STEER_SEGS ? STEER_SEGS : 0) + 1) * BINS;
 }
 
-hipError_t
-launch_steer(const uint64_t *ret, const uint8_t *faults, uint64_t count, uint32_t *index,
-	     uint64_t *starts, uint32_t *scratch, hipStream_t stream)
+bool
+launch_tile_scan(uint32_t *scratch, uint32_t ntiles, uint64_t *starts, hipStream_t stream)
 {
-	const uint32_t ntiles = tiles_of(count);
 	const bool two = ntiles > STEER_SEGS;
 	uint32_t *rows = scratch;
 	uint32_t *seg = rows + (size_t)ntiles * BINS;
 	uint32_t *tot = seg + (two ? (size_t)STEER_SEGS * BINS : 0);
 	const uint32_t seglen = (ntiles + STEER_SEGS - 1) / STEER_SEGS;
 	const uint32_t nseg = two ? (ntiles + seglen - 1) / seglen : 0;
-	hipLaunchKernelGGL(faults ? steer_count<true> : steer_count<false>, dim3(ntiles), dim3(THREADS), 0,
-			   stream, ret, faults, count, rows);
 	if (two)
 		hipLaunchKernelGGL(steer_seg_sum, dim3(nseg), dim3(THREADS), 0, stream, rows, ntiles, seglen,
 				   seg);
@@ -339,8 +279,20 @@ launch_steer(const uint64_t *ret, const uint8_t *faults, uint64_t count, uint32_
 	if (two)
 		hipLaunchKernelGGL(steer_scan_tiles, dim3(nseg), dim3(THREADS), 0, stream, rows, ntiles,
 				   seglen, seg, starts);
+	return two;
+}
+
+hipError_t
+launch_steer(const uint64_t *ret, const uint8_t *faults, uint64_t count, uint32_t *index,
+	     uint64_t *starts, uint32_t *scratch, hipStream_t stream)
+{
+	const uint32_t ntiles = tiles_of(count);
+	hipLaunchKernelGGL(faults ? steer_count<true> : steer_count<false>, dim3(ntiles), dim3(THREADS), 0,
+			   stream, ret, faults, count, scratch);
+	const bool two = launch_tile_scan(scratch, ntiles, starts, stream);
 	hipLaunchKernelGGL(faults ? steer_scatter<true> : steer_scatter<false>, dim3(ntiles),
-			   dim3(THREADS), 0, stream, ret, faults, count, rows, starts, two ? 1u : 0u, index);
+			   dim3(THREADS), 0, stream, ret, faults, count, scratch, starts, two ? 1u : 0u,
+			   index);
 	return hipGetLastError();
 }
 

@@ -15,6 +15,11 @@ constexpr uint32_t STEER_SEGS = 256;
 // Scratch of one steering call, in u32 words: a row of EBPF_HIST_BINS per tile, (two levels) per
 // segment, and one of class totals.  Any contents on entry.
 size_t steer_scratch_words(uint64_t count);
+// The tile scan on its own (group.hip's radix passes share it): scratch holds ntiles rows of class
+// counts, laid out as above.  Leaves starts[b] = the packets of the classes below b, for b in
+// [0, EBPF_HIST_BINS], and rows[t][b] = the packets of class b in the tiles before t, plus
+// starts[b] already iff it returns true (more than STEER_SEGS tiles).
+bool launch_tile_scan(uint32_t *scratch, uint32_t ntiles, uint64_t *starts, hipStream_t stream);
 // index[starts[b] .. starts[b+1]) = the packets of class b in ascending order (count >= 1,
 // count <= 0xffffffff); faults may be NULL.
 hipError_t launch_steer(const uint64_t *ret, const uint8_t *faults, uint64_t count, uint32_t *index,

@@ -127,6 +127,10 @@ FUNCS = {
     "ebpf_batch_steer": (_I, [_VP, _VP, _U64, _VP, _VP]),
     "ebpf_batch_steer_dev": (_I, [_I, _VP, _VP, _U64, _VP, _VP, _VP]),
     "ebpf_batch_select_dev": (_I, [_I, _VP, _VP, _U64, _VP, _VP]),
+    "ebpf_batch_group_tmp_bytes": (ctypes.c_size_t, [_U64, _U32]),
+    "ebpf_batch_group": (_I, [_VP, _VP, _U64, _U32, _U32, _VP, _U64, _VP, _VP, _VP]),
+    "ebpf_batch_group_dev": (_I, [_I, _VP, _VP, _U64, _U32, _U32, _VP, _U64, _VP, _VP, _VP, _VP,
+                                  ctypes.c_size_t, _VP]),
     "ebpf_batch_gather": (_I, [_VP, _VP, _U64, _U32, _VP, _U64, _VP]),
     "ebpf_batch_gather_dev": (_I, [_I, _VP, _VP, _U64, _U32, _VP, _U64, _VP, _VP]),
     "ebpf_batch_scatter": (_I, [_VP, _VP, _U64, _U32, _VP, _U64, _VP]),
@@ -567,6 +571,47 @@ def select_dev(device, data_ptr, count, stride, index_ptr, n, extents_ptr, offse
     b = PktBatch(data_ptr, offsets_ptr, count, stride, BATCH_EXTENTS if extents else 0)
     _check(lib().ebpf_batch_select_dev(device, ctypes.byref(b), index_ptr, n, extents_ptr,
                                        stream), "ebpf_batch_select_dev")
+
+
+def group_tmp_bytes(count, key_bits):
+    """ebpf_batch_group_tmp_bytes: the bytes of temporary device storage a group_dev call needs"""
+    return int(lib().ebpf_batch_group_tmp_bytes(count, key_bits))
+
+
+def group(ret, faults=None, key_shift=0, key_bits=32, group_cap=None):
+    """ebpf_batch_group on host arrays: the packets sorted stably by the key
+    (ret >> key_shift) & (2**key_bits - 1), faulted packets last.  Returns (index u32[count],
+    group_keys u64[group_cap], group_starts u64[group_cap + 1], info u64[2] = (groups,
+    unfaulted), code) with code 0 or errno.ENOSPC (more groups than ``group_cap``; the tables
+    then hold what fits).  ``group_cap`` None sizes the tables to fit."""
+    ret = np.ascontiguousarray(ret, dtype=np.uint64)
+    n = len(ret)
+    if faults is not None:
+        faults = np.ascontiguousarray(faults, dtype=np.uint8)
+        assert len(faults) == n
+    cap = n if group_cap is None else group_cap
+    index = np.zeros(n, dtype=np.uint32)
+    group_keys = np.zeros(cap, dtype=np.uint64)
+    group_starts = np.zeros(cap + 1, dtype=np.uint64)
+    info = np.zeros(2, dtype=np.uint64)
+    code = lib().ebpf_batch_group(ret.ctypes.data if n else None,
+                                  None if faults is None or not n else faults.ctypes.data, n,
+                                  key_shift, key_bits, index.ctypes.data if n else None, cap,
+                                  group_keys.ctypes.data if cap else None,
+                                  group_starts.ctypes.data, info.ctypes.data)
+    if code not in (0, errno.ENOSPC):
+        raise EbpfError(code, "ebpf_batch_group")
+    return index, group_keys, group_starts, info, code
+
+
+def group_dev(device, ret_ptr, faults_ptr, count, key_shift, key_bits, index_ptr, group_cap,
+              group_keys_ptr, group_starts_ptr, info_ptr, tmp_ptr, tmp_bytes, stream=None):
+    """ebpf_batch_group_dev: device pointers (ints); ``tmp_ptr`` is the caller's temporary
+    storage of at least group_tmp_bytes(count, key_bits); asynchronous on ``stream``."""
+    _check(lib().ebpf_batch_group_dev(device, ret_ptr, faults_ptr, count, key_shift, key_bits,
+                                      index_ptr, group_cap, group_keys_ptr, group_starts_ptr,
+                                      info_ptr, tmp_ptr, tmp_bytes, stream),
+           "ebpf_batch_group_dev")
 
 
 def gather(data, count, index, out_stride=0, stride=0, offsets=None, extents=False,

@@ -334,6 +334,79 @@ int ebpf_batch_steer_dev(int device, const uint64_t *ret_dev, const uint8_t *fau
 int ebpf_batch_select_dev(int device, const struct ebpf_pkt_batch *batch, const uint32_t *index_dev,
 			  uint64_t n, uint64_t *extents_dev, void *stream);
 
+/* Grouping a batch by key: steering for a verdict with more values than the histogram has bins (a
+ * load balancer's backend id, an RSS queue number, a flow hash whose packets a stateful second
+ * stage wants side by side in arrival order, an action packed beside a target).  The packets are
+ * sorted, stably, by a bit field of ret, and a table says where every group of equal keys begins:
+ *
+ *   ebpf_prog_run_batch_dev(ep, dev, &batch, ret, faults, hist, s);
+ *   ebpf_batch_group_dev(dev, ret, faults, batch.count, 0, 32, index, cap, keys, starts, info,
+ *                        tmp, ebpf_batch_group_tmp_bytes(batch.count, 32), s);
+ *   ebpf_batch_gather_dev(dev, &batch, index, batch.count, 64, out, ...);   (flows side by side)
+ *
+ * Key: the key of packet i is (ret[i] >> key_shift) & (2^key_bits - 1), with 1 <= key_bits <= 64
+ *   and key_shift + key_bits <= 64.  Bits of ret outside the field take no part, neither in the
+ *   order nor in deciding where a group ends.  Keys compare as unsigned numbers.
+ * Faulted packets: packet i is faulted iff faults is given and faults[i] != 0; its ret is then
+ *   not looked at, even where it is not 0.  With faults NULL no packet is faulted.
+ * Order: let U be the number of unfaulted packets.  index[0 .. U) holds them in ascending key
+ *   order, packets of equal key in ascending packet order (a stable sort: a flow's packets keep
+ *   their arrival order); index[U .. count) holds the faulted packets in ascending packet order.
+ *   index has count entries and is always written in full.
+ * Groups: a group is a maximal run of equal keys within index[0 .. U); let G be their number.
+ *   info has 2 entries, always written: info[0] = G, info[1] = U.  group_starts has group_cap + 1
+ *   entries and group_keys has group_cap.  For g < min(G, group_cap), group_keys[g] is the key of
+ *   group g (the field's value, shifted down) and group_starts[g] its first position in index; if
+ *   G <= group_cap then group_starts[G] = U as well, so group g is index[group_starts[g] ..
+ *   group_starts[g + 1]).  No other entry is written: none at or past min(G, group_cap) of
+ *   group_keys, none past min(G, group_cap) of group_starts, and group_starts[G] only when G <=
+ *   group_cap.  The table is complete iff info[0] <= group_cap (snprintf's rule, as the packed
+ *   gather's).  group_keys may be NULL: keys are then not written.  group_cap == 0 with
+ *   group_keys NULL only sorts and counts; group_starts then still has its one entry, written
+ *   (with U) iff G == 0, unless it is NULL too.
+ * The output is a function of the inputs alone: two calls on the same input give the same bytes.
+ * A group's list, or the whole index, is "any list" for ebpf_batch_select_dev,
+ * ebpf_batch_gather_dev, ebpf_batch_scatter_dev and ebpf_batch_merge_dev.
+ *
+ * ebpf_batch_group: host buffers, a plain stable sort; no GPU needed (the statement of what the
+ *   device function computes).  Returns ENOSPC when G > group_cap, with index, info and every
+ *   table entry that fits written.
+ * ebpf_batch_group_dev: every pointer is device memory on `device`; enqueued on `stream`
+ *   (hipStream_t, NULL = default stream), returns without synchronising and never waits for the
+ *   device, so a short table returns 0 and the caller compares info_dev[0] with its cap after the
+ *   stream.  A radix sort over digits of at most 8 bits, least significant first: ceil(key_bits /
+ *   8) passes, each moving every packet's key and index once.  tmp_dev is the caller's: at least
+ *   ebpf_batch_group_tmp_bytes(count, key_bits) bytes, 8-byte aligned, any contents on entry and
+ *   on return; it must outlive the call's work on the stream and may then be reused or freed.
+ *   Neither tmp_dev nor index_dev may overlap ret_dev, faults_dev, each other or the tables.  The
+ *   small per-tile tables (about 1 KiB per 4,096 packets) are the library's, per stream, shared
+ *   with ebpf_batch_steer_dev.  ret_dev, group_keys_dev, group_starts_dev and info_dev must be
+ *   8-byte aligned, index_dev 4-byte aligned, as their types say.
+ * ebpf_batch_group_tmp_bytes: host only, no GPU needed, a pure function:
+ *     n = count rounded up to a multiple of 64;  w = 4 if key_bits <= 32, else 8 (bytes a key)
+ *     n * w               if key_bits <= 8  (one pass: the sorted keys)
+ *     n * (2 * w + 4)     otherwise         (two key buffers and a second index buffer)
+ *   so at most 2 * (8 + 4) bytes a packet plus 2 * (8 + 4) * 63; 0 for count == 0, and 0 for
+ *   arguments the other two functions refuse (key_bits outside [1, 64], count > 0xffffffff).
+ * Both return 0; EINVAL for key_bits outside [1, 64] or key_shift + key_bits > 64, a NULL info,
+ * a NULL ret or index with count > 0, a NULL group_starts with group_cap > 0; then E2BIG for
+ * count > 0xffffffff (the packet index is 32 bits).  count == 0 succeeds: info = {0, 0}, and
+ * group_starts[0] = 0 if group_starts is given.  The device function then returns ENOSPC for
+ * tmp_bytes below ebpf_batch_group_tmp_bytes(count, key_bits), EINVAL for a NULL tmp_dev where
+ * that is not 0 — both known on the host, before the device is looked at and before any launch —
+ * then ENODEV (no GPU, or no such device), ENOMEM (no scratch) or EIO.  Neither changes the
+ * calling thread's current HIP device. */
+size_t ebpf_batch_group_tmp_bytes(uint64_t count, uint32_t key_bits);
+int ebpf_batch_group(const uint64_t *ret, const uint8_t *faults, uint64_t count,
+		     uint32_t key_shift, uint32_t key_bits, uint32_t *index,
+		     uint64_t group_cap, uint64_t *group_keys, uint64_t *group_starts,
+		     uint64_t *info);
+int ebpf_batch_group_dev(int device, const uint64_t *ret_dev, const uint8_t *faults_dev,
+			 uint64_t count, uint32_t key_shift, uint32_t key_bits,
+			 uint32_t *index_dev, uint64_t group_cap, uint64_t *group_keys_dev,
+			 uint64_t *group_starts_dev, uint64_t *info_dev,
+			 void *tmp_dev, size_t tmp_bytes, void *stream);
+
 /* Gathering packets into a dense batch: a list of n packets of `batch` (a class of a steered
  * batch, the whole steering index, any list of the caller's own: duplicates and any order are
  * fine) copied, in list order, into `out`.  A class can then leave the device on its own (a TX
