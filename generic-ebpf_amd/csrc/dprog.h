@@ -61,7 +61,7 @@ enum dp_kind : uint16_t {
 	DK_OVLINIT = 0x113,
 };
 // dp_launch.vflags.  (The assembly kernels test these, and the other dp_launch sub-fields named
-// below, by bit number: gen_interp.py keeps a copy of every value, and asm_runtime.cpp asserts
+// below, by bit number: gen_abi.py keeps a copy of every value, and asm_runtime.cpp asserts
 // the copies against this header.)
 #define DP_VF_OVERLAY 1u // the program reads its own stores into map values (DP_OVL_* below)
 #define DP_VF_VSTORE 2u  // the program has value-store sites

@@ -26,7 +26,7 @@ struct emitter {
 	//   words): from the packet dwords v22..v37 the staging left in registers, indexed by the
 	//   offset's dword (s_set_gpr_idx_on, M0) and aligned by its low bits — no memory access;
 	// * otherwise, in keep mode (AH_MODE_KEEP: gpu_runtime.cpp sets it for staged launches of
-	//   programs with these loads), from the wave's transposed LDS packet buffer (gen_interp.py
+	//   programs with these loads), from the wave's transposed LDS packet buffer (gen_emit.py
 	//   lds_pkt_read) when every running lane's bytes lie in its 64;
 	// * else the interpreter's handler body h (generic load, faults), spliced in by the code
 	//   generator.
@@ -798,7 +798,7 @@ struct emitter {
 		return true;
 	}
 
-	// ---- EXIT with r0 known: result and verdict bin set here, then .Lr_exit_k (gen_interp.py)
+	// ---- EXIT with r0 known: result and verdict bin set here, then .Lr_exit_k (gen_routines.py)
 	void exit_known(uint64_t r0, uint32_t exitk_off, bool call)
 	{
 		mov32(V_RES, (uint32_t)r0);

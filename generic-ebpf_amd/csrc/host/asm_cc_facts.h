@@ -13,7 +13,7 @@
 namespace {
 
 // ---------------------------------------------------------------- registers
-// The kernels' registers this code names.  gen_interp.py assigns them and writes them into
+// The kernels' registers this code names.  gen_abi.py assigns them and writes them into
 // asm_handlers.h; these are aliases, so a register that moves there moves here with it.  (eBPF
 // register rK in v[2K:2K+1] is the one convention both sides spell out: emitter::L / Hi.)
 const int S_MODE = AH_S_MODE;          // the mode word (AH_MODE_* bits)
@@ -155,7 +155,7 @@ struct mapinfo {
 };
 
 // ---------------------------------------------------------------- families
-// The generator (gen_interp.py) states each family's class and its index within the class
+// The generator (gen_abi.py) states each family's class and its index within the class
 // (asm_handlers.h ah_fam_class / ah_fam_idx); nothing here depends on the order it registers them in.
 inline int
 class_of(int fam)

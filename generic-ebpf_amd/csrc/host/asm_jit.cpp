@@ -6,7 +6,7 @@
 //   s_mov_b32 s10..s15, <operand>       only the entry registers the handler body reads
 //   <handler body bytes>                copied from the assembled interpreter image
 //   s_waitcnt lgkmcnt(0)                if the body leaves an LDS read outstanding
-//   conditional tail / branch           see gen_interp.py jit_templates()
+//   conditional tail / branch           see gen_jit.py jit_templates()
 // into the reserved area of a private copy of the code object (ebpf_jit_area), which is then
 // loaded as its own module.  Handler bodies reach the shared routines (fault, exit, udiv,
 // check, lookup, schedule) relative to .Lcb, whose offset is the same in every copy, so the

@@ -353,7 +353,7 @@ launch(struct ebpf_prog *ep, dprog_device *dp, const dp_launch &L0, hipStream_t 
 		dp->last_layout = mode;
 		// the staged kernels' keep mode (compiled and interpreted programs): a program that
 		// loads its packet at run-time offsets reads them from the wave's LDS packet buffer
-		// (gen_interp.py h_ldx_pktv), so the next group's DMA waits for the group's end
+		// (gen_handlers.py h_ldx_pktv), so the next group's DMA waits for the group's end
 		if (mode == 1 && ep->xlated->asm_keep)
 			L.vflags |= DP_VF_KEEP;
 		// general kernels: header staging, and the headers kept in LDS too (DP_PKTLDS_HDRKEEP;

@@ -120,7 +120,7 @@ constexpr uint32_t kProbeWorkgroups = 5;
 // The assembly interpreter's code objects (build/asm_image.cpp): mode 1 = staged 64-B kernels,
 // mode 0 = general kernels.  Image 3 is mode 1 for the interpreter itself (variant 2): one
 // result group per burst, 64 VGPRs and s0..s73, so 8 workgroups per CU are resident instead of 6
-// (gen_interp.py NSGPR_INTERP).
+// (gen_abi.py NSGPR_INTERP).
 constexpr int kModes = 2;
 constexpr int kInterpStagedImage = 3;
 extern __attribute__((visibility("hidden"))) const unsigned char ebpf_asm_hsaco_m1[], ebpf_asm_hsaco_m0[],

@@ -344,3 +344,61 @@ def test_write_phasing_code(tmp_path):
     rt = open(os.path.join(root, "host", "asm_runtime.cpp")).read()
     assert "X(wphase, AH_L_WPHASE)" in re.search(r"#define AH_LAUNCH_FIELDS\(X\) (.*)", hdr).group(1)
     assert "static_assert(offsetof(dp_launch, member) == off," in rt and "\nAH_LAUNCH_FIELDS(X)\n" in rt
+
+
+ASM_DIR = os.path.join(os.path.dirname(__file__), "..", "generic-ebpf_amd", "csrc", "asm")
+ASM_MODULES = sorted(f[:-3] for f in os.listdir(ASM_DIR) if f.endswith(".py"))
+
+
+def test_asm_images_order_independent(monkeypatch):
+    """An image's text is a function of its description alone (gen_image.py Image): the general
+    image generated alone, the three in table order and the three in reverse order give equal
+    text per image, and equal handler tables throughout (the host uses one set for all)."""
+    monkeypatch.syspath_prepend(ASM_DIR)
+    import gen_interp
+    from gen_image import IMAGES
+    assert [i.name for i in IMAGES] == ["m1", "m0", "m3"]
+    alone = gen_interp.generate(IMAGES[1])
+    forward = {i.name: gen_interp.generate(i) for i in IMAGES}
+    backward = {i.name: gen_interp.generate(i) for i in reversed(IMAGES)}
+    assert forward["m0"][0] == alone[0]
+    for name in forward:
+        assert forward[name][0] == backward[name][0], name
+        assert forward[name][1] == backward[name][1] == alone[1], name
+    assert len({text for text, _ in forward.values()}) == 3
+
+
+def test_asm_generator_import_writes_nothing(tmp_path):
+    """Importing the generator's modules writes no file and does not look at sys.argv: only
+    main() does either."""
+    import sys
+    script = (
+        "import os, sys\n"
+        "class Trap(list):\n"
+        "    def _no(self, *a): raise AssertionError('sys.argv read at import')\n"
+        "    __getitem__ = __iter__ = __len__ = _no\n"
+        "sys.argv = Trap()\n"
+        "sys.path.insert(0, %r)\n"
+        "for m in %r: __import__(m)\n"
+        "assert os.listdir('.') == [], os.listdir('.')\n" % (os.path.abspath(ASM_DIR), ASM_MODULES))
+    assert "gen_interp" in ASM_MODULES and len(ASM_MODULES) > 1
+    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
+    r = subprocess.run([sys.executable, "-c", script], cwd=tmp_path, env=env, capture_output=True,
+                       text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-600:]
+    assert os.listdir(tmp_path) == []
+
+
+def test_asm_image_digest_two_processes():
+    """tools/asm_image_digest.py (the byte-identity check of a change to the generator) gives the
+    same lines in two processes: one per output file, for the default setting."""
+    import sys
+    tool = os.path.join(os.path.dirname(__file__), "..", "tools", "asm_image_digest.py")
+    procs = [subprocess.Popen([sys.executable, tool, "--default-only"], stdout=subprocess.PIPE,
+                              stderr=subprocess.PIPE, text=True) for _ in range(2)]
+    (a, aerr), (b, berr) = (p.communicate(timeout=300) for p in procs)
+    assert procs[0].returncode == 0 and procs[1].returncode == 0, (aerr[-400:], berr[-400:])
+    assert a == b
+    lines = a.splitlines()
+    assert [ln.split()[:2] for ln in lines] == [["-", f] for f in ("m1.s", "m0.s", "m3.s", "asm_handlers.h")]
+    assert all(len(ln.split()[3]) == 64 and int(ln.split()[2]) > 0 for ln in lines)
