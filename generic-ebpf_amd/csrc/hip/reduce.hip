@@ -1,0 +1,577 @@
+// reduce.hip — per-segment reductions over a list of a batch's packets (ebpf_batch_reduce_dev):
+// bytes, and the sum, minimum, maximum and OR of a bit field of ret.  DESIGN.md §2 "Reducing per
+// group".
+//
+// A segmented reduction whose cost follows the list, not the shape of its segments:
+//   reduce_tiles   one workgroup per tile of STEER_TILE list positions.  Two of its waves find the
+//                  segments of the tile's first and last position (a 64-way search of seg_starts);
+//                  the segments that begin in the tile mark their first position in LDS (empty
+//                  ones mark nothing, so any number of them at one position costs their reads
+//                  alone).  A thread owns 16 consecutive positions: it reduces them run by run,
+//                  the runs that end in it are closed with what a segmented scan over the threads
+//                  carries in, and a segment that begins and ends in the tile is written at once
+//                  (a tile that closes many of them stages them in LDS and stores them in
+//                  segment order: write_staged).
+//                  What is open at the tile's edges goes to two scratch rows: the positions before
+//                  the tile's first marked one, and those from its last marked one on.
+//   reduce_carry   one workgroup: the same segmented scan over the tiles' rows, two levels (a
+//                  thread walks a run of tiles).  Every tile edge is crossed by at most one
+//                  segment; the tile in which such a segment ends writes it.
+//   reduce_empty   a thread per segment: an empty segment's identities.
+// Every output entry below R is written by exactly one thread of one kernel, no atomic decides
+// anything and no workgroup waits for another: the output is a function of the input alone.
+// Positions at or past seg_starts[R] add identities, positions before seg_starts[0] add to a run
+// that nobody writes.  A table that is not non-decreasing, or that ends past n, gives unspecified
+// sums, but every position is clamped to n, every segment number that is written is below R, and
+// the marks stay inside the tile.
+#include <hip/hip_runtime.h>
+
+#include "ebpf_gpu.h"
+#include "hip/batch_places.h"
+#include "host/reduce.h"
+#include "host/steer.h"
+
+namespace {
+
+constexpr uint32_t TILE = STEER_TILE;
+constexpr uint32_t PER_THREAD = TILE / THREADS;
+constexpr uint32_t NOHEAD = ~0u;         // no segment begins here (a segment's number is below it)
+constexpr uint32_t CARRY_THREADS = 1024; // reduce_carry's one workgroup
+constexpr uint32_t ROW = REDUCE_ROW_WORDS;
+static_assert(PER_THREAD == 16, "a thread's positions are one padded LDS row");
+// A tile that closes this many segments or more writes them out through LDS, STAGE at a time.
+constexpr uint32_t STAGE_MIN = 256;
+constexpr uint32_t STAGE = TILE / 2;
+
+typedef struct ebpf_batch_sums sums;
+
+// A run of list entries reduced: of segment g if flag, else of the segment that was open before
+// the run began.
+struct part {
+	uint64_t bytes, sum, mn, mx, bits;
+	uint32_t g, flag;
+};
+
+__device__ __forceinline__ part
+nothing()
+{
+	return {0, 0, ~0ull, 0, 0, 0, 0};
+}
+
+// a's entries, then b's, of one segment
+template <bool LENS, bool VALS>
+__device__ __forceinline__ void
+add(part &a, const part &b)
+{
+	if (LENS)
+		a.bytes += b.bytes;
+	if (VALS) {
+		a.sum += b.sum;
+		a.mn = b.mn < a.mn ? b.mn : a.mn;
+		a.mx = b.mx > a.mx ? b.mx : a.mx;
+		a.bits |= b.bits;
+	}
+}
+
+// The segmented scan's operator: run a, then run b.  A segment that begins in b closes a.
+template <bool LENS, bool VALS>
+__device__ __forceinline__ part
+join(const part &a, const part &b)
+{
+	if (b.flag)
+		return b;
+	part r = a;
+	add<LENS, VALS>(r, b);
+	return r;
+}
+
+template <bool LENS, bool VALS>
+__device__ __forceinline__ part
+lane_up(const part &p, uint32_t d)
+{
+	part r = p;
+	r.g = __shfl_up(p.g, d);
+	r.flag = __shfl_up(p.flag, d);
+	if (LENS)
+		r.bytes = __shfl_up((unsigned long long)p.bytes, d);
+	if (VALS) {
+		r.sum = __shfl_up((unsigned long long)p.sum, d);
+		r.mn = __shfl_up((unsigned long long)p.mn, d);
+		r.mx = __shfl_up((unsigned long long)p.mx, d);
+		r.bits = __shfl_up((unsigned long long)p.bits, d);
+	}
+	return r;
+}
+
+// The join of the runs of the threads before this one, in thread order.  wtot: a part per wave,
+// in LDS.
+template <bool LENS, bool VALS, uint32_t NW>
+__device__ __forceinline__ part
+carry_in(const part &mine, part *wtot)
+{
+	const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+	part inc = mine; // inclusive scan over the wave
+#pragma unroll
+	for (uint32_t d = 1; d < 64; d <<= 1) {
+		const part up = lane_up<LENS, VALS>(inc, d);
+		if (lane >= d)
+			inc = join<LENS, VALS>(up, inc);
+	}
+	if (lane == 63)
+		wtot[w] = inc;
+	__syncthreads();
+	part before = nothing();
+	for (uint32_t q = 0; q < NW; q++) {
+		const part s = wtot[q];
+		if (q < w)
+			before = join<LENS, VALS>(before, s);
+	}
+	const part prev = lane_up<LENS, VALS>(inc, 1);
+	return lane == 0 ? before : join<LENS, VALS>(before, prev);
+}
+
+// The number of segments reduced (ebpf_gpu.h): a short table holds no end for its last group.
+__device__ __forceinline__ uint64_t
+segments_of(uint64_t cap, const uint64_t *__restrict__ nseg)
+{
+	if (nseg == nullptr)
+		return cap;
+	const uint64_t g = *nseg;
+	return g <= cap ? g : (cap != 0 ? cap - 1 : 0);
+}
+
+// How many of S[0 .. m) are <= p, for a non-decreasing S: a wave's 64-way search, every lane the
+// same answer.  For any other S it still ends, with an answer in [0, m], having read only S[0 .. m).
+__device__ __forceinline__ uint64_t
+upper(const uint64_t *__restrict__ S, uint64_t m, uint64_t p)
+{
+	const uint32_t lane = threadIdx.x & 63;
+	uint64_t lo = 0, hi = m;
+	while (lo < hi) {
+		const uint64_t step = (hi - lo + 63) / 64;
+		const uint64_t at = lo + lane * step;
+		const bool le = at < hi && S[at] <= p;
+		const uint64_t b = ~__ballot(le);
+		const uint32_t c = b == 0 ? 64u : (uint32_t)__builtin_ctzll(b); // the probes <= p, from lo on
+		if (c == 0)
+			break;
+		const uint64_t end = lo + c * step;
+		lo += (c - 1) * step + 1;
+		hi = end < hi ? end : hi;
+	}
+	return lo;
+}
+
+// Where position q of a tile sits in LDS: a thread's 16 positions are a row, and a word of
+// padding a row keeps both the tile-order and the row-order accesses off one another's banks.
+__device__ __forceinline__ uint32_t
+slot(uint32_t q)
+{
+	return q + (q >> 4);
+}
+
+template <bool LENS, bool VALS>
+__device__ __forceinline__ void
+store_row(uint64_t *__restrict__ row, const part &p)
+{
+	if (LENS)
+		row[0] = p.bytes;
+	if (VALS) {
+		row[1] = p.sum;
+		row[2] = p.mn;
+		row[3] = p.mx;
+		row[4] = p.bits;
+	}
+}
+
+template <bool LENS, bool VALS>
+__device__ __forceinline__ part
+load_row(const uint64_t *__restrict__ row)
+{
+	part p = nothing();
+	if (LENS)
+		p.bytes = row[0];
+	if (VALS) {
+		p.sum = row[1];
+		p.mn = row[2];
+		p.mx = row[3];
+		p.bits = row[4];
+	}
+	return p;
+}
+
+// segment g's results, if it is one of the R
+template <bool LENS, bool VALS>
+__device__ __forceinline__ void
+write_out(const sums &out, uint64_t g, uint64_t R, const part &p)
+{
+	if (g >= R)
+		return;
+	if (LENS)
+		out.bytes[g] = p.bytes;
+	if (VALS) {
+		if (out.sum != nullptr)
+			out.sum[g] = p.sum;
+		if (out.min != nullptr)
+			out.min[g] = p.mn;
+		if (out.max != nullptr)
+			out.max[g] = p.mx;
+		if (out.bits != nullptr)
+			out.bits[g] = p.bits;
+	}
+}
+
+// One statistic on its own: 0 bytes, 1 sum, 2 min, 3 max, 4 bits.
+template <int STAT>
+__device__ __forceinline__ uint64_t
+ident()
+{
+	return STAT == 2 ? ~0ull : 0;
+}
+
+template <int STAT>
+__device__ __forceinline__ uint64_t
+fold(uint64_t a, uint64_t b)
+{
+	return STAT <= 1 ? a + b : STAT == 2 ? (b < a ? b : a) : STAT == 3 ? (b > a ? b : a) : a | b;
+}
+
+// One output of the segments that a tile closes, written in segment order: the tile's e-th
+// marked position closes the segment that the one before it began, number sg[e - 1].  The thread
+// walks its entries for this statistic alone, puts what it closes into sv (STAGE results at a
+// time), and the workgroup then stores sv to neighbouring entries of dst from neighbouring lanes:
+// a thread that closes 16 one-entry segments would otherwise store them one by one, 8 bytes a
+// lane at a 128-byte stride.  hb: the marked positions before the thread's; closed: the segments
+// the tile closes.  Every thread of the workgroup calls it.
+template <int STAT>
+__device__ __forceinline__ void
+write_staged(uint64_t *__restrict__ dst, uint64_t R, const uint32_t (&seg)[PER_THREAD],
+	     const uint32_t (&len)[PER_THREAD], const uint64_t (&val)[PER_THREAD],
+	     const bool (&has)[PER_THREAD], uint64_t carried, uint32_t hb, uint32_t closed,
+	     const uint32_t *sg, uint64_t *sv)
+{
+	if (dst == nullptr) // (the same for every thread)
+		return;
+	for (uint32_t base = 0; base < closed; base += STAGE) {
+		uint64_t acc = carried;
+		uint32_t e = hb;
+#pragma unroll
+		for (uint32_t k = 0; k < PER_THREAD; k++) {
+			if (seg[k] != NOHEAD) {
+				// (unsigned: false for e - 1 below base as well)
+				if (e != 0 && e - 1 - base < STAGE)
+					sv[e - 1 - base] = acc;
+				acc = ident<STAT>();
+				e++;
+			}
+			acc = fold<STAT>(acc, STAT == 0 ? len[k] : has[k] ? val[k] : ident<STAT>());
+		}
+		__syncthreads();
+		const uint32_t m = closed - base < STAGE ? closed - base : STAGE;
+		for (uint32_t r = threadIdx.x; r < m; r += THREADS) {
+			const uint64_t g = sg[base + r];
+			if (g < R)
+				dst[g] = sv[r];
+		}
+		__syncthreads();
+	}
+}
+
+// rows: per tile, {bytes, sum, min, max, bits, does a segment begin in the tile} over the
+// positions before the first that begins one (all of them if none does), then {..., that
+// segment} over the positions from the last such on.  count >= 1, n >= 1.
+template <bool LENS, bool VALS>
+__global__ void __launch_bounds__(THREADS, 3) // (three waves a SIMD: the gathers want them)
+reduce_tiles(places f, const uint64_t *__restrict__ ret, uint32_t val_shift, uint64_t val_mask,
+	     const uint32_t *__restrict__ index, uint64_t n, const uint64_t *__restrict__ S,
+	     uint64_t cap, const uint64_t *__restrict__ nseg, sums out, uint64_t *__restrict__ rows)
+{
+	__shared__ uint32_t sidx[TILE + TILE / 16]; // the tile's list entries
+	// the segment that begins at a position, or NOHEAD; later STAGE results on their way out
+	__shared__ __attribute__((aligned(8))) uint32_t sseg[TILE + TILE / 16];
+	static_assert(STAGE * sizeof(uint64_t) <= sizeof(sseg), "the staged results fit");
+	__shared__ part wtot[WAVES];
+	__shared__ uint64_t wsum[WAVES];
+	__shared__ uint64_t range[2];
+	const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+	const uint64_t R = segments_of(cap, nseg);
+	uint64_t *row = rows + (size_t)blockIdx.x * 2 * ROW;
+	const uint64_t first = (uint64_t)blockIdx.x * TILE;
+	// the list ends where the last segment does
+	uint64_t end = R != 0 ? S[R] : 0;
+	end = end < n ? end : n;
+	if (first >= end) { // (the same for every thread)
+		if (tid == 0) {
+			store_row<LENS, VALS>(row, nothing());
+			row[ROW - 1] = 0;
+		}
+		return;
+	}
+	const uint64_t last = (first + TILE < end ? first + TILE : end) - 1;
+	uint32_t raw[PER_THREAD];
+#pragma unroll
+	for (uint32_t k = 0; k < PER_THREAD; k++) {
+		const uint64_t j = first + k * THREADS + tid;
+		raw[k] = index[j < end ? j : end - 1];
+	}
+	if (w < 2) {
+		const uint64_t u = upper(S, R, w == 0 ? first : last);
+		if (lane == 0)
+			range[w] = u;
+	}
+#pragma unroll
+	for (uint32_t k = 0; k < PER_THREAD; k++) {
+		sidx[slot(k * THREADS + tid)] = raw[k];
+		sseg[slot(k * THREADS + tid)] = NOHEAD;
+	}
+	__syncthreads();
+	// Segments [lo, hi) are those of the tile's positions: lo the one that holds `first` (0 if
+	// none does yet), hi past the one that holds `last`.  One that is not empty marks its start.
+	const uint64_t lo = range[0] != 0 ? range[0] - 1 : 0;
+	const uint64_t hi = range[1] < R ? range[1] : R;
+	for (uint64_t g = lo + tid; g < hi; g += THREADS) {
+		uint64_t a = S[g], b = S[g + 1];
+		a = a < n ? a : n;
+		b = b < n ? b : n;
+		if (a < b && a >= first && a - first < TILE)
+			sseg[slot((uint32_t)(a - first))] = (uint32_t)g;
+	}
+	// The thread's 16 entries: the ret and offsets loads are issued together, as lens_of's.
+	uint32_t idx[PER_THREAD], len[PER_THREAD] = {};
+	uint64_t val[PER_THREAD] = {}; // the entry's value field
+	bool has[PER_THREAD];
+	{
+		uint64_t s[PER_THREAD], e[PER_THREAD];
+#pragma unroll
+		for (uint32_t k = 0; k < PER_THREAD; k++) {
+			idx[k] = sidx[slot(tid * PER_THREAD + k)];
+			has[k] = first + tid * PER_THREAD + k < end && idx[k] < f.count;
+		}
+		if (VALS) {
+#pragma unroll
+			for (uint32_t k = 0; k < PER_THREAD; k++)
+				val[k] = ret[idx[k] < f.count ? idx[k] : f.count - 1];
+#pragma unroll
+			for (uint32_t k = 0; k < PER_THREAD; k++)
+				val[k] = (val[k] >> val_shift) & val_mask;
+		}
+		if (LENS) {
+#pragma unroll
+			for (uint32_t k = 0; k < PER_THREAD; k++) {
+				s[k] = e[k] = 0;
+				if (!has[k])
+					continue;
+				if (f.offsets == nullptr) {
+					e[k] = f.stride;
+				} else if (f.extents) {
+					s[k] = f.offsets[2 * (uint64_t)idx[k]];
+					e[k] = f.offsets[2 * (uint64_t)idx[k] + 1];
+				} else {
+					s[k] = f.offsets[idx[k]];
+					e[k] = f.offsets[(uint64_t)idx[k] + 1];
+				}
+			}
+#pragma unroll
+			for (uint32_t k = 0; k < PER_THREAD; k++) {
+				const uint64_t d = e[k] - s[k];
+				len[k] = (e[k] < s[k] || (d >> 32) != 0) ? 0u : (uint32_t)d;
+			}
+		}
+	}
+	__syncthreads();
+	uint32_t seg[PER_THREAD];
+#pragma unroll
+	for (uint32_t k = 0; k < PER_THREAD; k++)
+		seg[k] = sseg[slot(tid * PER_THREAD + k)];
+	// entry k as a part (identities for an entry with no value, and past the list's end)
+	auto entry = [&](uint32_t k) {
+		part p = nothing();
+		if (LENS)
+			p.bytes = len[k];
+		if (VALS && has[k])
+			p.sum = p.mn = p.mx = p.bits = val[k];
+		return p;
+	};
+	// what leaves the thread on its right: its last run
+	part mine = nothing();
+#pragma unroll
+	for (uint32_t k = 0; k < PER_THREAD; k++) {
+		if (seg[k] != NOHEAD) {
+			mine = nothing();
+			mine.flag = 1;
+			mine.g = seg[k];
+		}
+		add<LENS, VALS>(mine, entry(k));
+	}
+	part cur = carry_in<LENS, VALS, WAVES>(mine, wtot);
+	// The marked positions before this thread's, and the tile's.  All but the last close a
+	// segment inside the tile; many of them go out through LDS (every thread decides alike).
+	uint32_t marked = 0;
+#pragma unroll
+	for (uint32_t k = 0; k < PER_THREAD; k++)
+		marked += seg[k] != NOHEAD;
+	uint64_t all;
+	const uint32_t hb = (uint32_t)block_scan(marked, wsum, all);
+	const uint32_t closed = all != 0 ? (uint32_t)all - 1 : 0;
+	const bool staged = closed >= STAGE_MIN;
+	if (staged) {
+		// (sidx and sseg are free: every thread has its entries and marks in registers)
+		uint32_t *sg = sidx;
+		uint64_t *sv = reinterpret_cast<uint64_t *>(sseg);
+		uint32_t e = hb;
+#pragma unroll
+		for (uint32_t k = 0; k < PER_THREAD; k++)
+			if (seg[k] != NOHEAD)
+				sg[e++] = seg[k];
+		if (LENS)
+			write_staged<0>(out.bytes, R, seg, len, val, has, cur.bytes, hb, closed, sg, sv);
+		if (VALS) {
+			write_staged<1>(out.sum, R, seg, len, val, has, cur.sum, hb, closed, sg, sv);
+			write_staged<2>(out.min, R, seg, len, val, has, cur.mn, hb, closed, sg, sv);
+			write_staged<3>(out.max, R, seg, len, val, has, cur.mx, hb, closed, sg, sv);
+			write_staged<4>(out.bits, R, seg, len, val, has, cur.bits, hb, closed, sg, sv);
+		}
+	}
+#pragma unroll
+	for (uint32_t k = 0; k < PER_THREAD; k++) {
+		if (seg[k] != NOHEAD) {
+			if (cur.flag) {
+				if (!staged)
+					write_out<LENS, VALS>(out, cur.g, R, cur);
+			} else { // the tile's first: what came before it belongs to an earlier tile's segment
+				store_row<LENS, VALS>(row, cur);
+			}
+			cur = nothing();
+			cur.flag = 1;
+			cur.g = seg[k];
+		}
+		add<LENS, VALS>(cur, entry(k));
+	}
+	if (tid == THREADS - 1) {
+		row[ROW - 1] = cur.flag;
+		if (cur.flag) {
+			store_row<LENS, VALS>(row + ROW, cur);
+			row[2 * ROW - 1] = cur.g;
+		} else {
+			store_row<LENS, VALS>(row, cur);
+		}
+	}
+}
+
+// What tile t hands to the tiles after it.
+template <bool LENS, bool VALS>
+__device__ __forceinline__ part
+tile_tail(const uint64_t *__restrict__ rows, uint32_t t)
+{
+	const uint64_t *row = rows + (size_t)t * 2 * ROW;
+	const bool begins = row[ROW - 1] != 0;
+	part p = load_row<LENS, VALS>(begins ? row + ROW : row);
+	p.flag = begins;
+	p.g = begins ? (uint32_t)row[2 * ROW - 1] : 0;
+	return p;
+}
+
+// One workgroup: thread s walks tiles [s * seglen, (s + 1) * seglen) twice, first for what the
+// run hands on, then, with what the threads before it hand in, to close the segments that cross
+// tile edges: each is written where the next segment begins, the last one by the last tile.
+template <bool LENS, bool VALS>
+__global__ void __launch_bounds__(CARRY_THREADS)
+reduce_carry(const uint64_t *__restrict__ rows, uint32_t ntiles, uint64_t cap,
+	     const uint64_t *__restrict__ nseg, sums out)
+{
+	__shared__ part wtot[CARRY_THREADS / 64];
+	const uint32_t tid = threadIdx.x;
+	const uint64_t R = segments_of(cap, nseg);
+	const uint32_t seglen = (ntiles + CARRY_THREADS - 1) / CARRY_THREADS;
+	const uint32_t t0 = min(tid * seglen, ntiles), t1 = min(t0 + seglen, ntiles);
+	part mine = nothing();
+	for (uint32_t t = t0; t < t1; t++)
+		mine = join<LENS, VALS>(mine, tile_tail<LENS, VALS>(rows, t));
+	part cur = carry_in<LENS, VALS, CARRY_THREADS / 64>(mine, wtot);
+	for (uint32_t t = t0; t < t1; t++) {
+		const uint64_t *row = rows + (size_t)t * 2 * ROW;
+		const part head = load_row<LENS, VALS>(row);
+		add<LENS, VALS>(cur, head);
+		if (row[ROW - 1] != 0) {
+			if (cur.flag)
+				write_out<LENS, VALS>(out, cur.g, R, cur);
+			cur = tile_tail<LENS, VALS>(rows, t);
+		}
+	}
+	if (t0 < t1 && t1 == ntiles && cur.flag)
+		write_out<LENS, VALS>(out, cur.g, R, cur);
+}
+
+// A thread per segment: an empty one's results.  (n == 0: every segment is empty.)
+__global__ void __launch_bounds__(THREADS)
+reduce_empty(const uint64_t *__restrict__ S, uint64_t n, uint64_t cap,
+	     const uint64_t *__restrict__ nseg, sums out)
+{
+	const uint64_t g = (uint64_t)blockIdx.x * THREADS + threadIdx.x;
+	if (g >= segments_of(cap, nseg))
+		return;
+	uint64_t a = S[g], b = S[g + 1];
+	a = a < n ? a : n;
+	b = b < n ? b : n;
+	if (a < b)
+		return;
+	if (out.bytes != nullptr)
+		out.bytes[g] = 0;
+	if (out.sum != nullptr)
+		out.sum[g] = 0;
+	if (out.min != nullptr)
+		out.min[g] = ~0ull;
+	if (out.max != nullptr)
+		out.max[g] = 0;
+	if (out.bits != nullptr)
+		out.bits[g] = 0;
+}
+
+template <bool LENS, bool VALS>
+void
+launch_typed(const places &f, const uint64_t *ret, uint32_t val_shift, uint64_t val_mask,
+	     const uint32_t *index, uint64_t n, const uint64_t *S, uint64_t cap, const uint64_t *nseg,
+	     const sums &out, uint64_t *rows, hipStream_t stream)
+{
+	const uint32_t ntiles = (uint32_t)((n + TILE - 1) / TILE);
+	hipLaunchKernelGGL((reduce_tiles<LENS, VALS>), dim3(ntiles), dim3(THREADS), 0, stream, f, ret,
+			   val_shift, val_mask, index, n, S, cap, nseg, out, rows);
+	hipLaunchKernelGGL((reduce_carry<LENS, VALS>), dim3(1), dim3(CARRY_THREADS), 0, stream, rows,
+			   ntiles, cap, nseg, out);
+}
+
+} // namespace
+
+size_t
+reduce_scratch_bytes(uint64_t n)
+{
+	return (size_t)((n + TILE - 1) / TILE) * 2 * ROW * sizeof(uint64_t);
+}
+
+hipError_t
+launch_reduce(const struct ebpf_pkt_batch *batch, const uint64_t *ret, uint64_t count,
+	      uint32_t val_shift, uint32_t val_bits, const uint32_t *index, uint64_t n,
+	      const uint64_t *seg_starts, uint64_t seg_cap, const uint64_t *nseg,
+	      const struct ebpf_batch_sums &out, uint64_t *scratch, hipStream_t stream)
+{
+	const bool lens = out.bytes != nullptr;
+	const bool vals = out.sum != nullptr || out.min != nullptr || out.max != nullptr ||
+			  out.bits != nullptr;
+	if (n != 0) {
+		const places f = lens ? places_of(*batch) : places{nullptr, count, 0, 0};
+		const uint64_t mask = val_bits >= 64 ? ~0ull : (1ull << val_bits) - 1;
+		if (lens && vals)
+			launch_typed<true, true>(f, ret, val_shift, mask, index, n, seg_starts, seg_cap, nseg,
+						 out, scratch, stream);
+		else if (lens)
+			launch_typed<true, false>(f, ret, val_shift, mask, index, n, seg_starts, seg_cap, nseg,
+						  out, scratch, stream);
+		else
+			launch_typed<false, true>(f, ret, val_shift, mask, index, n, seg_starts, seg_cap, nseg,
+						  out, scratch, stream);
+	}
+	const uint32_t blocks = (uint32_t)((seg_cap + THREADS - 1) / THREADS);
+	hipLaunchKernelGGL(reduce_empty, dim3(blocks), dim3(THREADS), 0, stream, seg_starts, n, seg_cap,
+			   nseg, out);
+	return hipGetLastError();
+}

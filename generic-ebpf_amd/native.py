@@ -66,6 +66,12 @@ class PktBatch(ctypes.Structure):
                 ("flags", ctypes.c_uint32)]
 
 
+class BatchSums(ctypes.Structure):
+    """struct ebpf_batch_sums: the outputs of a reduce call, each NULL or seg_cap u64"""
+    _fields_ = [("bytes", ctypes.c_void_p), ("sum", ctypes.c_void_p), ("min", ctypes.c_void_p),
+                ("max", ctypes.c_void_p), ("bits", ctypes.c_void_p)]
+
+
 class BatchStats(ctypes.Structure):
     _fields_ = [("packets", ctypes.c_uint64), ("faulted", ctypes.c_uint64),
                 ("hist", ctypes.c_uint64 * EBPF_HIST_BINS), ("kernel_ms", ctypes.c_double),
@@ -131,6 +137,9 @@ FUNCS = {
     "ebpf_batch_group": (_I, [_VP, _VP, _U64, _U32, _U32, _VP, _U64, _VP, _VP, _VP]),
     "ebpf_batch_group_dev": (_I, [_I, _VP, _VP, _U64, _U32, _U32, _VP, _U64, _VP, _VP, _VP, _VP,
                                   ctypes.c_size_t, _VP]),
+    "ebpf_batch_reduce": (_I, [_VP, _VP, _U64, _U32, _U32, _VP, _U64, _VP, _U64, _VP, _VP]),
+    "ebpf_batch_reduce_dev": (_I, [_I, _VP, _VP, _U64, _U32, _U32, _VP, _U64, _VP, _U64, _VP, _VP,
+                                   _VP]),
     "ebpf_batch_gather": (_I, [_VP, _VP, _U64, _U32, _VP, _U64, _VP]),
     "ebpf_batch_gather_dev": (_I, [_I, _VP, _VP, _U64, _U32, _VP, _U64, _VP, _VP]),
     "ebpf_batch_scatter": (_I, [_VP, _VP, _U64, _U32, _VP, _U64, _VP]),
@@ -612,6 +621,64 @@ def group_dev(device, ret_ptr, faults_ptr, count, key_shift, key_bits, index_ptr
                                       index_ptr, group_cap, group_keys_ptr, group_starts_ptr,
                                       info_ptr, tmp_ptr, tmp_bytes, stream),
            "ebpf_batch_group_dev")
+
+
+SUMS = ("bytes", "sum", "min", "max", "bits")   # struct ebpf_batch_sums' members, in order
+
+
+def reduce(index, seg_starts, ret=None, val_shift=0, val_bits=64, count=None, stride=0,
+           offsets=None, extents=False, nseg=None, want=SUMS):
+    """ebpf_batch_reduce on host arrays: per segment index[seg_starts[g]:seg_starts[g + 1]] of the
+    list, the outputs named in ``want``: "bytes" (the packets' lengths, of the batch (count,
+    stride, offsets, extents) as run_batch takes it; no packet data is needed), and "sum", "min",
+    "max", "bits" of the field (ret >> val_shift) & (2**val_bits - 1).  ``seg_starts`` has
+    seg_cap + 1 entries; ``nseg`` (None: every one of the seg_cap segments) is the number of
+    segments as ebpf_batch_group's info[0] gives it.  Returns (bytes, sum, min, max, bits, code):
+    u64[seg_cap] each, or None where not wanted; entries at or past the segments reduced are 0.
+    code is 0 or errno.EINVAL for a table that decreases or ends past the list."""
+    index = np.ascontiguousarray(index, dtype=np.uint32)
+    seg_starts = np.ascontiguousarray(seg_starts, dtype=np.uint64)
+    cap = max(len(seg_starts) - 1, 0)
+    if ret is not None:
+        ret = np.ascontiguousarray(ret, dtype=np.uint64)
+    if count is None:
+        count = 0 if ret is None else len(ret)
+    offs = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
+    b = None
+    if "bytes" in want:   # (data: never read, but a batch with packets names some)
+        b = PktBatch(1 if count else None, None if offs is None else offs.ctypes.data, count,
+                     stride, BATCH_EXTENTS if extents else 0)
+    outs = [np.zeros(cap, dtype=np.uint64) if name in want else None for name in SUMS]
+    sums = BatchSums(*[None if o is None or not cap else o.ctypes.data for o in outs])
+    ns = None if nseg is None else np.array([nseg], dtype=np.uint64)
+    code = lib().ebpf_batch_reduce(None if b is None else ctypes.byref(b),
+                                   None if ret is None or not len(ret) else ret.ctypes.data,
+                                   count, val_shift, val_bits,
+                                   index.ctypes.data if len(index) else None, len(index),
+                                   seg_starts.ctypes.data if len(seg_starts) else None, cap,
+                                   None if ns is None else ns.ctypes.data, ctypes.byref(sums))
+    if code not in (0, errno.EINVAL):
+        raise EbpfError(code, "ebpf_batch_reduce")
+    return (*outs, code)
+
+
+def reduce_dev(device, ret_ptr, count, val_shift, val_bits, index_ptr, n, seg_starts_ptr, seg_cap,
+               nseg_ptr=None, bytes_ptr=None, sum_ptr=None, min_ptr=None, max_ptr=None,
+               bits_ptr=None, stride=0, offsets_ptr=None, extents=False, data_ptr=None,
+               stream=None):
+    """ebpf_batch_reduce_dev: device pointers (ints); the outputs that are wanted are given, each
+    seg_cap u64.  The batch (count, stride, offsets_ptr, extents) as run_batch_dev takes it is
+    needed for ``bytes_ptr`` alone; ``data_ptr`` is never read (None: a stand-in).  Asynchronous
+    on ``stream``."""
+    b = None
+    if bytes_ptr is not None:
+        b = PktBatch(data_ptr or (1 if count else None), offsets_ptr, count, stride,
+                     BATCH_EXTENTS if extents else 0)
+    sums = BatchSums(bytes_ptr, sum_ptr, min_ptr, max_ptr, bits_ptr)
+    _check(lib().ebpf_batch_reduce_dev(device, None if b is None else ctypes.byref(b), ret_ptr,
+                                       count, val_shift, val_bits, index_ptr, n, seg_starts_ptr,
+                                       seg_cap, nseg_ptr, ctypes.byref(sums), stream),
+           "ebpf_batch_reduce_dev")
 
 
 def gather(data, count, index, out_stride=0, stride=0, offsets=None, extents=False,

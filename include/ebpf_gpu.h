@@ -407,6 +407,88 @@ int ebpf_batch_group_dev(int device, const uint64_t *ret_dev, const uint8_t *fau
 			 uint64_t *group_starts_dev, uint64_t *info_dev,
 			 void *tmp_dev, size_t tmp_bytes, void *stream);
 
+/* Reducing a list per segment: how much each group carried.  Once flows lie side by side (a
+ * grouped index) or classes do (a steering index), these functions reduce, per group or class, the
+ * packets' lengths and a bit field of their verdicts, without per-packet data crossing to the
+ * host: bytes per flow or per steering class, the OR of a flags field over a flow, a flow's
+ * largest sequence number, the sum of a payload-length field per backend:
+ *
+ *   ebpf_batch_group_dev(dev, ret, faults, batch.count, 0, 32, index, cap, keys, starts, info,
+ *                        tmp, tmp_bytes, s);
+ *   sums = {bytes, sum, NULL, max, NULL};                          (cap entries each)
+ *   ebpf_batch_reduce_dev(dev, &batch, ret, batch.count, 32, 16, index, batch.count, starts, cap,
+ *                         info, &sums, s);
+ *   (read info and the sums' first min(info[0], cap) entries)
+ *
+ * List and segments: index[0 .. n) is any list of packets of the batch — a grouped index, a
+ *   steering index, the caller's own; duplicates and any order are fine.  Segment g is
+ *   index[seg_starts[g] .. seg_starts[g + 1]).  The number R of segments reduced is seg_cap when
+ *   nseg is NULL (the steering case: seg_starts = starts, seg_cap = EBPF_HIST_BINS); else *nseg
+ *   when *nseg <= seg_cap; else seg_cap - 1 (0 for seg_cap == 0): a short group table holds no end
+ *   for its last group.  So ebpf_batch_group_dev's group_starts, group_cap and info (as nseg) plug
+ *   in as they stand, after it on the same stream, with nothing read on the host, and the result
+ *   is complete iff info[0] <= group_cap, as the table's is.  seg_starts[0 .. R] is read: it is
+ *   non-decreasing and seg_starts[R] <= n.  Entries at or past R of any output are not written.
+ *   Positions of the list that no segment covers take no part: those before seg_starts[0] and
+ *   those at or past seg_starts[R] (the faulted tail [U, count) of a grouped index).
+ * Per listed entry j, with i = index[j]: its length is the gather's len_j (the batch's packet i by
+ *   the run functions' rule: 0 for an end below the start or 2^32 bytes or more past it, and 0 for
+ *   i >= count); its value is (ret[i] >> val_shift) & (2^val_bits - 1), with 1 <= val_bits <= 64
+ *   and val_shift + val_bits <= 64.  An entry with i >= count has no value: it is left out of sum,
+ *   min, max and bits.  faults is not consulted: a faulted packet's ret is what the run functions
+ *   left there.
+ * Outputs (struct ebpf_batch_sums): each member is NULL (not wanted: it costs nothing) or has
+ *   seg_cap entries.  For g < R: bytes[g] = the sum of the segment's lengths; sum[g] = the sum of
+ *   its values modulo 2^64; min[g], max[g] = its smallest and largest value as unsigned numbers;
+ *   bits[g] = the OR of its values.  A segment with no entry, or no entry that has a value, gives
+ *   the identities: bytes 0, sum 0, min UINT64_MAX, max 0, bits 0.
+ * Which arguments may be NULL: batch iff out->bytes is NULL; ret iff sum, min, max and bits all
+ *   are; with all five NULL the call succeeds and does nothing.  batch->data is never read, and
+ *   of batch->offsets only the listed packets' entries.
+ * The output is a function of the inputs alone: it does not depend on what the output arrays held
+ * on entry, and two calls on the same input give the same bytes.
+ *
+ * ebpf_batch_reduce: host buffers, a plain loop per segment; no GPU needed (the statement of what
+ *   the device function computes).  It also returns EINVAL, with nothing written, when
+ *   seg_starts[0 .. R] is not non-decreasing or seg_starts[R] > n.
+ * ebpf_batch_reduce_dev: every pointer (batch->offsets, ret_dev, index_dev, seg_starts_dev,
+ *   nseg_dev and the members of *out; batch and out themselves are host structs) is device memory
+ *   on `device`; enqueued on `stream` (hipStream_t, NULL = default stream), returns without
+ *   synchronising and never waits for the device.  It cannot look at the table: for one that is
+ *   not non-decreasing or that ends past n, the first R entries of the outputs are unspecified,
+ *   but every position is clamped to n: nothing outside index[0 .. n), ret[0 .. count), the listed
+ *   packets' offsets entries and seg_starts[0 .. R] is read, and nothing but those output entries
+ *   is written.  The cost follows the list's length and the table's, not the shape of the
+ *   segments: one segment over the whole list, n segments of one entry and thousands of empty
+ *   segments at one position take about the time of the reads.  Temporary storage is the
+ *   library's, per stream, shared with ebpf_batch_steer_dev and ebpf_batch_group_dev: 96 bytes per
+ *   4,096 list entries.  The outputs may not overlap the inputs or each other.  ret_dev,
+ *   seg_starts_dev, nseg_dev, batch->offsets and the outputs must be 8-byte aligned, index_dev
+ *   4-byte aligned, as their types say.
+ * Both return 0; EINVAL for a NULL out, for val_bits outside [1, 64] or val_shift + val_bits > 64
+ * when ret is used (sum, min, max or bits wanted), a NULL ret or batch where an output needs it, a
+ * batch that the run functions would refuse, batch->count != count when batch is given, a NULL
+ * index with n > 0, a NULL seg_starts with seg_cap > 0; then E2BIG for n, count or seg_cap above
+ * 0xffffffff.  All of these are known on the host, before the device is looked at.  The device
+ * function then returns ENODEV (no GPU, or no such device), ENOMEM (no scratch) or EIO.  Neither
+ * changes the calling thread's current HIP device. */
+struct ebpf_batch_sums {   /* each NULL (not wanted) or seg_cap entries */
+	uint64_t *bytes;   /* sum of the listed packets' lengths */
+	uint64_t *sum;     /* sum of the value field, modulo 2^64 */
+	uint64_t *min;     /* smallest value, unsigned; UINT64_MAX for no value */
+	uint64_t *max;     /* largest value, unsigned; 0 for no value */
+	uint64_t *bits;    /* OR of the values */
+};
+int ebpf_batch_reduce(const struct ebpf_pkt_batch *batch, const uint64_t *ret, uint64_t count,
+		      uint32_t val_shift, uint32_t val_bits, const uint32_t *index, uint64_t n,
+		      const uint64_t *seg_starts, uint64_t seg_cap, const uint64_t *nseg,
+		      const struct ebpf_batch_sums *out);
+int ebpf_batch_reduce_dev(int device, const struct ebpf_pkt_batch *batch, const uint64_t *ret_dev,
+			  uint64_t count, uint32_t val_shift, uint32_t val_bits,
+			  const uint32_t *index_dev, uint64_t n, const uint64_t *seg_starts_dev,
+			  uint64_t seg_cap, const uint64_t *nseg_dev,
+			  const struct ebpf_batch_sums *out, void *stream);
+
 /* Gathering packets into a dense batch: a list of n packets of `batch` (a class of a steered
  * batch, the whole steering index, any list of the caller's own: duplicates and any order are
  * fine) copied, in list order, into `out`.  A class can then leave the device on its own (a TX
