@@ -40,7 +40,20 @@ def _cat(parts, dtype):
     return allv, offs
 
 
-def save(path, cases):
+def _write_npz(path, arrays):
+    """np.savez_compressed's format with every member's time stamp fixed, so that the same
+    arrays give the same file byte for byte."""
+    import zipfile
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as z:
+        for key, arr in arrays.items():
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o600 << 16
+            with z.open(info, "w", force_zip64=True) as f:
+                np.lib.format.write_array(f, np.asanyarray(arr), allow_pickle=False)
+
+
+def save(path, cases, reproducible=False):
     codes, code_off = _cat([np.frombuffer(c.code, dtype=np.uint8) for c in cases], np.uint8)
     data, data_off = _cat([c.data for c in cases], np.uint8)
     edata, _ = _cat([c.expect_data for c in cases], np.uint8)
@@ -52,7 +65,8 @@ def save(path, cases):
     mrow = [(i, k, vs, me) for i, c in enumerate(cases) for k, (vs, me, _) in enumerate(c.maps)]
     mdat, mdat_off = _cat([np.frombuffer(d, dtype=np.uint8) for c in cases for (_, _, d) in c.maps],
                           np.uint8)
-    np.savez_compressed(
+    write = (lambda p, **arrays: _write_npz(p, arrays)) if reproducible else np.savez_compressed
+    write(
         path, names=np.array([c.name for c in cases]), code=codes, code_off=code_off,
         data=data, data_off=data_off, expect_data=edata, expect_r0=r0, r0_off=r0_off,
         offsets=offs, offsets_off=offs_off,
@@ -64,7 +78,8 @@ def save(path, cases):
 
 
 def load(path):
-    z = np.load(path, allow_pickle=False)
+    with np.load(path, allow_pickle=False) as f:
+        z = {k: f[k] for k in f.files}     # (each member decompressed once, not per case)
     out = []
     maps_rows = z["maps"]
     mi = 0

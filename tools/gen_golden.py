@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
 """Generate tests/golden/*.npz from the GENUINE reference interpreter (container only).
 
-The reference libebpf.so is the one the survey built from /root/reference in a scratch copy
-(/tmp/refbuild); this script does not build or copy the reference.  It
-compiles oracle/refgen/ref_harness.c against it (outputs only under oracle/_ref/), writes each
-case to a binary case file, runs the harness (every packet twice under two stack poisons), and
-keeps a case only if no packet read undefined state.
+The reference libebpf.so is built by oracle/Makefile's _ref/libebpf.so target in a writable copy
+of the reference tree under oracle/_ref/refbuild (about two minutes,
+offline); `make -C oracle _ref/ref_harness`, which this script runs, builds it when it is
+missing and compiles oracle/refgen/ref_harness.c against it (outputs only under oracle/_ref/).
+The script writes each case to a binary case file, runs the harness (every packet twice under
+two stack poisons), and keeps a case only if no packet read undefined state; in the `edges`
+group (tests/edgeprogs.py, written to tests/golden/edges/edges.npz) an undefined read is an
+error instead, since none of those cases may go.
 
-Usage: python tools/gen_golden.py [--quick] [--rand N] [--pkts N]
+Usage: python tools/gen_golden.py [--quick] [--rand N] [--pkts N] [--only GROUP]
 """
 import argparse
 import os
@@ -151,8 +154,21 @@ def workload_cases(n):
     return out
 
 
+def edges_cases():
+    """tests/edgeprogs.py under reference semantics (the programs that divide by zero are not
+    among them: the reference crashes there)."""
+    import edgeprogs
+    return [goldens.Case(c.name, c.code, [], [], c.packets(64), c.count, 64, None)
+            for c in edgeprogs.build(edgeprogs.SEM_REFERENCE)]
+
+
+EDGES_PATH = os.path.join(goldens.GOLDEN_DIR, "edges", "edges.npz")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--only", metavar="GROUP", help="write this group's fixture alone "
+                    "(kat, rand, workloads, edges)")
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--rand", type=int, default=200, help="random-program cases")
     ap.add_argument("--pkts", type=int, default=2048, help="packets per workload case")
@@ -160,22 +176,35 @@ def main():
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "_ref/ref_harness"])
     os.makedirs(goldens.GOLDEN_DIR, exist_ok=True)
     groups = {
-        "kat": kat_cases(),
-        "rand": rand_cases(40 if args.quick else args.rand, 1000),
-        "workloads": workload_cases(512 if args.quick else args.pkts),
+        "kat": kat_cases,
+        "rand": lambda: rand_cases(40 if args.quick else args.rand, 1000),
+        "workloads": lambda: workload_cases(512 if args.quick else args.pkts),
+        "edges": edges_cases,
     }
+    if args.only is not None:
+        if args.only not in groups:
+            ap.error("no group %r" % args.only)
+        groups = {args.only: groups[args.only]}
     with tempfile.TemporaryDirectory() as tmp:
-        for gname, cases in groups.items():
+        for gname, make in groups.items():
             keep = []
-            for c in cases:
+            for c in make():
                 r0, undef, after = run_reference(c, tmp)
+                if undef.any() and gname == "edges":
+                    sys.exit("edges: %s: %d packets read undefined state" % (
+                        c.name, int((undef != 0).sum())))
                 if undef.any():
                     print("drop %s: %d packets read undefined state" % (c.name, int((undef != 0).sum())))
                     continue
                 c.expect_r0, c.expect_data = r0, after
                 keep.append(c)
-            path = os.path.join(goldens.GOLDEN_DIR, gname + ".npz")
-            goldens.save(path, keep)
+            if gname == "edges":   # a subdirectory (not among goldens.all_golden_files())
+                os.makedirs(os.path.dirname(EDGES_PATH), exist_ok=True)
+                goldens.save(EDGES_PATH, keep, reproducible=True)
+                path = EDGES_PATH
+            else:
+                path = os.path.join(goldens.GOLDEN_DIR, gname + ".npz")
+                goldens.save(path, keep)
             print("%s: %d cases -> %s (%d bytes)" % (gname, len(keep), path, os.path.getsize(path)))
 
 
