@@ -1,6 +1,8 @@
-// batch_places.h — what gather.hip and scatter.hip share: where a batch keeps its packets, the
-// length rule, a workgroup's scan, and the 16-byte load / store forms.  Device code only; every
-// file that includes it is compiled on its own, so everything here is file-local.
+// batch_places.h — what gather.hip, scatter.hip, reduce.hip and scan.hip share: where a batch
+// keeps its packets, the length rule, a workgroup's scan, the 16-byte load / store forms, and what
+// the segmented kernels need of a list's segments (their number, the 64-way search, a tile's LDS
+// slots, a thread's lengths and values).  Device code only; every file that includes it is compiled
+// on its own, so everything here is file-local.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -108,6 +110,88 @@ block_scan(uint64_t v, uint64_t *wsum, uint64_t &total)
 	__syncthreads();
 	total = all;
 	return before + inc - v;
+}
+
+// The number of segments of a list (ebpf_gpu.h): a short table holds no end for its last group.
+__device__ __forceinline__ uint64_t
+segments_of(uint64_t cap, const uint64_t *__restrict__ nseg)
+{
+	if (nseg == nullptr)
+		return cap;
+	const uint64_t g = *nseg;
+	return g <= cap ? g : (cap != 0 ? cap - 1 : 0);
+}
+
+// How many of S[0 .. m) are <= p, for a non-decreasing S: a wave's 64-way search, every lane the
+// same answer.  For any other S it still ends, with an answer in [0, m], having read only S[0 .. m).
+__device__ __forceinline__ uint64_t
+upper(const uint64_t *__restrict__ S, uint64_t m, uint64_t p)
+{
+	const uint32_t lane = threadIdx.x & 63;
+	uint64_t lo = 0, hi = m;
+	while (lo < hi) {
+		const uint64_t step = (hi - lo + 63) / 64;
+		const uint64_t at = lo + lane * step;
+		const bool le = at < hi && S[at] <= p;
+		const uint64_t b = ~__ballot(le);
+		const uint32_t c = b == 0 ? 64u : (uint32_t)__builtin_ctzll(b); // the probes <= p, from lo on
+		if (c == 0)
+			break;
+		const uint64_t end = lo + c * step;
+		lo += (c - 1) * step + 1;
+		hi = end < hi ? end : hi;
+	}
+	return lo;
+}
+
+// Where position q of a tile sits in LDS: a thread's 16 positions are a row, and a word of
+// padding a row keeps both the tile-order and the row-order accesses off one another's banks.
+__device__ __forceinline__ uint32_t
+slot(uint32_t q)
+{
+	return q + (q >> 4);
+}
+
+// A thread's N list entries idx[k]: their lengths (0 where !has[k]: past the list's end, or past
+// the batch's) and their value fields of ret (ret has f.count >= 1 entries; an entry past the
+// batch reads the last one, and its value is not used).  The ret loads are issued together, then
+// the offsets loads, as lens_of's.
+template <bool LENS, bool VALS, uint32_t N>
+__device__ __forceinline__ void
+fields_of(const places &f, const uint64_t *__restrict__ ret, uint32_t val_shift, uint64_t val_mask,
+	  const uint32_t (&idx)[N], const bool (&has)[N], uint32_t (&len)[N], uint64_t (&val)[N])
+{
+	uint64_t s[N], e[N];
+	if (VALS) {
+#pragma unroll
+		for (uint32_t k = 0; k < N; k++)
+			val[k] = ret[idx[k] < f.count ? idx[k] : f.count - 1];
+#pragma unroll
+		for (uint32_t k = 0; k < N; k++)
+			val[k] = (val[k] >> val_shift) & val_mask;
+	}
+	if (LENS) {
+#pragma unroll
+		for (uint32_t k = 0; k < N; k++) {
+			s[k] = e[k] = 0;
+			if (!has[k])
+				continue;
+			if (f.offsets == nullptr) {
+				e[k] = f.stride;
+			} else if (f.extents) {
+				s[k] = f.offsets[2 * (uint64_t)idx[k]];
+				e[k] = f.offsets[2 * (uint64_t)idx[k] + 1];
+			} else {
+				s[k] = f.offsets[idx[k]];
+				e[k] = f.offsets[(uint64_t)idx[k] + 1];
+			}
+		}
+#pragma unroll
+		for (uint32_t k = 0; k < N; k++) {
+			const uint64_t d = e[k] - s[k];
+			len[k] = (e[k] < s[k] || (d >> 32) != 0) ? 0u : (uint32_t)d;
+		}
+	}
 }
 
 // 16 bytes at a 16-byte-aligned address

@@ -130,46 +130,6 @@ carry_in(const part &mine, part *wtot)
 	return lane == 0 ? before : join<LENS, VALS>(before, prev);
 }
 
-// The number of segments reduced (ebpf_gpu.h): a short table holds no end for its last group.
-__device__ __forceinline__ uint64_t
-segments_of(uint64_t cap, const uint64_t *__restrict__ nseg)
-{
-	if (nseg == nullptr)
-		return cap;
-	const uint64_t g = *nseg;
-	return g <= cap ? g : (cap != 0 ? cap - 1 : 0);
-}
-
-// How many of S[0 .. m) are <= p, for a non-decreasing S: a wave's 64-way search, every lane the
-// same answer.  For any other S it still ends, with an answer in [0, m], having read only S[0 .. m).
-__device__ __forceinline__ uint64_t
-upper(const uint64_t *__restrict__ S, uint64_t m, uint64_t p)
-{
-	const uint32_t lane = threadIdx.x & 63;
-	uint64_t lo = 0, hi = m;
-	while (lo < hi) {
-		const uint64_t step = (hi - lo + 63) / 64;
-		const uint64_t at = lo + lane * step;
-		const bool le = at < hi && S[at] <= p;
-		const uint64_t b = ~__ballot(le);
-		const uint32_t c = b == 0 ? 64u : (uint32_t)__builtin_ctzll(b); // the probes <= p, from lo on
-		if (c == 0)
-			break;
-		const uint64_t end = lo + c * step;
-		lo += (c - 1) * step + 1;
-		hi = end < hi ? end : hi;
-	}
-	return lo;
-}
-
-// Where position q of a tile sits in LDS: a thread's 16 positions are a row, and a word of
-// padding a row keeps both the tile-order and the row-order accesses off one another's banks.
-__device__ __forceinline__ uint32_t
-slot(uint32_t q)
-{
-	return q + (q >> 4);
-}
-
 template <bool LENS, bool VALS>
 __device__ __forceinline__ void
 store_row(uint64_t *__restrict__ row, const part &p)
@@ -340,44 +300,12 @@ reduce_tiles(places f, const uint64_t *__restrict__ ret, uint32_t val_shift, uin
 	uint32_t idx[PER_THREAD], len[PER_THREAD] = {};
 	uint64_t val[PER_THREAD] = {}; // the entry's value field
 	bool has[PER_THREAD];
-	{
-		uint64_t s[PER_THREAD], e[PER_THREAD];
 #pragma unroll
-		for (uint32_t k = 0; k < PER_THREAD; k++) {
-			idx[k] = sidx[slot(tid * PER_THREAD + k)];
-			has[k] = first + tid * PER_THREAD + k < end && idx[k] < f.count;
-		}
-		if (VALS) {
-#pragma unroll
-			for (uint32_t k = 0; k < PER_THREAD; k++)
-				val[k] = ret[idx[k] < f.count ? idx[k] : f.count - 1];
-#pragma unroll
-			for (uint32_t k = 0; k < PER_THREAD; k++)
-				val[k] = (val[k] >> val_shift) & val_mask;
-		}
-		if (LENS) {
-#pragma unroll
-			for (uint32_t k = 0; k < PER_THREAD; k++) {
-				s[k] = e[k] = 0;
-				if (!has[k])
-					continue;
-				if (f.offsets == nullptr) {
-					e[k] = f.stride;
-				} else if (f.extents) {
-					s[k] = f.offsets[2 * (uint64_t)idx[k]];
-					e[k] = f.offsets[2 * (uint64_t)idx[k] + 1];
-				} else {
-					s[k] = f.offsets[idx[k]];
-					e[k] = f.offsets[(uint64_t)idx[k] + 1];
-				}
-			}
-#pragma unroll
-			for (uint32_t k = 0; k < PER_THREAD; k++) {
-				const uint64_t d = e[k] - s[k];
-				len[k] = (e[k] < s[k] || (d >> 32) != 0) ? 0u : (uint32_t)d;
-			}
-		}
+	for (uint32_t k = 0; k < PER_THREAD; k++) {
+		idx[k] = sidx[slot(tid * PER_THREAD + k)];
+		has[k] = first + tid * PER_THREAD + k < end && idx[k] < f.count;
 	}
+	fields_of<LENS, VALS>(f, ret, val_shift, val_mask, idx, has, len, val);
 	__syncthreads();
 	uint32_t seg[PER_THREAD];
 #pragma unroll

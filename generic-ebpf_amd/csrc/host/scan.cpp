@@ -1,0 +1,143 @@
+// scan.cpp — running totals per segment over a list of a batch's packets (ebpf_gpu.h "Running
+// totals per segment"): on the host (ebpf_batch_scan, the statement of the semantics) and on the
+// device (ebpf_batch_scan_dev, scan.hip).
+#include "gather.h"
+#include "runtime.h"
+#include "scan.h"
+
+namespace {
+
+inline bool
+wants_lengths(const struct ebpf_batch_scans &o)
+{
+	return o.bytes_before != nullptr || o.over != nullptr;
+}
+
+inline bool
+wants_nothing(const struct ebpf_batch_scans &o)
+{
+	return o.rank == nullptr && o.sum_before == nullptr && !wants_lengths(o);
+}
+
+int
+scan_args(const struct ebpf_pkt_batch *batch, const uint64_t *ret, uint64_t count,
+	  uint32_t val_shift, uint32_t val_bits, const uint32_t *index, uint64_t n,
+	  const uint64_t *seg_starts, uint64_t seg_cap, const uint64_t *budgets,
+	  const struct ebpf_batch_scans *out)
+{
+	if (out == nullptr)
+		return fail(EINVAL, "out is NULL");
+	if (out->sum_before != nullptr) {
+		if (ret == nullptr)
+			return fail(EINVAL, "ret is NULL where sum_before is wanted");
+		if (val_bits < 1 || val_bits > 64 || val_shift > 64 - val_bits)
+			return fail(EINVAL, "val_bits outside [1, 64], or val_shift + val_bits above 64");
+	}
+	if (wants_lengths(*out) && batch == nullptr)
+		return fail(EINVAL, "batch is NULL where bytes_before or over is wanted");
+	if (out->over != nullptr && budgets == nullptr)
+		return fail(EINVAL, "budgets is NULL where over is wanted");
+	if (batch != nullptr) {
+		// (EBPF_BATCH_HIST_OVERWRITE: as ebpf_batch_reduce, no concern of the packets' places)
+		int err = validate_batch(batch, EBPF_BATCH_HIST_OVERWRITE);
+		if (err)
+			return err;
+		if (batch->count != count)
+			return fail(EINVAL, "batch->count differs from count");
+	}
+	if (n != 0 && index == nullptr)
+		return fail(EINVAL, "index is NULL with n > 0");
+	if (seg_cap != 0 && seg_starts == nullptr)
+		return fail(EINVAL, "seg_starts is NULL with seg_cap > 0");
+	if (n > 0xffffffffull || count > 0xffffffffull || seg_cap > 0xffffffffull)
+		return fail(E2BIG, "n, count or seg_cap above 2^32 - 1");
+	return 0;
+}
+
+} // namespace
+
+// A plain loop per segment: the reference for the device kernels.
+EBPF_EXPORT int
+ebpf_batch_scan(const struct ebpf_pkt_batch *batch, const uint64_t *ret, uint64_t count,
+		uint32_t val_shift, uint32_t val_bits, const uint32_t *index, uint64_t n,
+		const uint64_t *seg_starts, uint64_t seg_cap, const uint64_t *nseg,
+		const uint64_t *budgets, const struct ebpf_batch_scans *out)
+{
+	int err = scan_args(batch, ret, count, val_shift, val_bits, index, n, seg_starts, seg_cap,
+			    budgets, out);
+	if (err)
+		return err;
+	const uint64_t R = nseg == nullptr ? seg_cap
+			   : *nseg <= seg_cap ? *nseg
+					      : (seg_cap != 0 ? seg_cap - 1 : 0);
+	for (uint64_t g = 0; g < R; g++)
+		if (seg_starts[g] > seg_starts[g + 1])
+			return fail(EINVAL, "seg_starts decreases");
+	if (seg_cap != 0 && seg_starts[R] > n)
+		return fail(EINVAL, "seg_starts ends past n");
+	// the positions that no segment covers
+	for (uint64_t j = 0; j < n; j++) {
+		if (R != 0 && j >= seg_starts[0] && j < seg_starts[R])
+			continue;
+		if (out->rank != nullptr)
+			out->rank[j] = 0;
+		if (out->bytes_before != nullptr)
+			out->bytes_before[j] = 0;
+		if (out->sum_before != nullptr)
+			out->sum_before[j] = 0;
+		if (out->over != nullptr)
+			out->over[j] = 0;
+	}
+	const uint64_t mask = val_bits >= 64 ? ~0ull : (1ull << val_bits) - 1;
+	for (uint64_t g = 0; g < R; g++) {
+		uint64_t bytes = 0, sum = 0;
+		for (uint64_t j = seg_starts[g]; j < seg_starts[g + 1]; j++) {
+			const uint32_t i = index[j];
+			uint64_t len = 0;
+			if (wants_lengths(*out)) {
+				uint64_t s;
+				len = packet_span(*batch, i, &s);
+			}
+			if (out->rank != nullptr)
+				out->rank[j] = (uint32_t)(j - seg_starts[g]);
+			if (out->bytes_before != nullptr)
+				out->bytes_before[j] = bytes;
+			if (out->sum_before != nullptr)
+				out->sum_before[j] = sum;
+			if (out->over != nullptr)
+				out->over[j] = bytes + len > budgets[g];
+			bytes += len;
+			if (out->sum_before != nullptr && i < count)
+				sum += (ret[i] >> val_shift) & mask;
+		}
+	}
+	return 0;
+}
+
+EBPF_EXPORT int
+ebpf_batch_scan_dev(int device, const struct ebpf_pkt_batch *batch, const uint64_t *ret_dev,
+		    uint64_t count, uint32_t val_shift, uint32_t val_bits, const uint32_t *index_dev,
+		    uint64_t n, const uint64_t *seg_starts_dev, uint64_t seg_cap,
+		    const uint64_t *nseg_dev, const uint64_t *budgets_dev,
+		    const struct ebpf_batch_scans *out, void *stream)
+{
+	int err = scan_args(batch, ret_dev, count, val_shift, val_bits, index_dev, n, seg_starts_dev,
+			    seg_cap, budgets_dev, out);
+	if (err || (err = check_device(device)))
+		return err;
+	if (n == 0 || wants_nothing(*out))
+		return 0;
+	device_guard dg;
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	hipError_t e = hipSetDevice(device);
+	if (e != hipSuccess)
+		return hip_fail(e, "hipSetDevice");
+	uint32_t *scratch = nullptr;
+	// (the steering rows' buffer: calls on a stream run in order, so they share it)
+	const bool rows = count != 0 && (wants_lengths(*out) || out->sum_before != nullptr);
+	if (rows && (err = steer_acquire(device, st, scan_scratch_bytes(n), &scratch)))
+		return fail(err, "scan scratch");
+	e = launch_scan(batch, ret_dev, count, val_shift, val_bits, index_dev, n, seg_starts_dev,
+			seg_cap, nseg_dev, budgets_dev, *out, reinterpret_cast<uint64_t *>(scratch), st);
+	return e == hipSuccess ? 0 : hip_fail(e, "scan kernels");
+}

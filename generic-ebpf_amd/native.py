@@ -72,6 +72,12 @@ class BatchSums(ctypes.Structure):
                 ("max", ctypes.c_void_p), ("bits", ctypes.c_void_p)]
 
 
+class BatchScans(ctypes.Structure):
+    """struct ebpf_batch_scans: the outputs of a scan call, each NULL or n entries"""
+    _fields_ = [("rank", ctypes.c_void_p), ("bytes_before", ctypes.c_void_p),
+                ("sum_before", ctypes.c_void_p), ("over", ctypes.c_void_p)]
+
+
 class BatchStats(ctypes.Structure):
     _fields_ = [("packets", ctypes.c_uint64), ("faulted", ctypes.c_uint64),
                 ("hist", ctypes.c_uint64 * EBPF_HIST_BINS), ("kernel_ms", ctypes.c_double),
@@ -140,6 +146,9 @@ FUNCS = {
     "ebpf_batch_reduce": (_I, [_VP, _VP, _U64, _U32, _U32, _VP, _U64, _VP, _U64, _VP, _VP]),
     "ebpf_batch_reduce_dev": (_I, [_I, _VP, _VP, _U64, _U32, _U32, _VP, _U64, _VP, _U64, _VP, _VP,
                                    _VP]),
+    "ebpf_batch_scan": (_I, [_VP, _VP, _U64, _U32, _U32, _VP, _U64, _VP, _U64, _VP, _VP, _VP]),
+    "ebpf_batch_scan_dev": (_I, [_I, _VP, _VP, _U64, _U32, _U32, _VP, _U64, _VP, _U64, _VP, _VP, _VP,
+                                 _VP]),
     "ebpf_batch_gather": (_I, [_VP, _VP, _U64, _U32, _VP, _U64, _VP]),
     "ebpf_batch_gather_dev": (_I, [_I, _VP, _VP, _U64, _U32, _VP, _U64, _VP, _VP]),
     "ebpf_batch_scatter": (_I, [_VP, _VP, _U64, _U32, _VP, _U64, _VP]),
@@ -679,6 +688,73 @@ def reduce_dev(device, ret_ptr, count, val_shift, val_bits, index_ptr, n, seg_st
                                        count, val_shift, val_bits, index_ptr, n, seg_starts_ptr,
                                        seg_cap, nseg_ptr, ctypes.byref(sums), stream),
            "ebpf_batch_reduce_dev")
+
+
+SCANS = ("rank", "bytes_before", "sum_before", "over")   # struct ebpf_batch_scans' members, in order
+_SCAN_TYPES = {"rank": np.uint32, "bytes_before": np.uint64, "sum_before": np.uint64,
+               "over": np.uint8}
+
+
+def scan(index, seg_starts, ret=None, val_shift=0, val_bits=64, count=None, stride=0,
+         offsets=None, extents=False, nseg=None, budgets=None, want=SCANS):
+    """ebpf_batch_scan on host arrays: per position j of the list, within its segment
+    index[seg_starts[g]:seg_starts[g + 1]], the outputs named in ``want``: "rank" (the segment's
+    entries before j), "bytes_before" (their lengths, of the batch (count, stride, offsets,
+    extents) as run_batch takes it; no packet data is needed), "sum_before" (their values of the
+    field (ret >> val_shift) & (2**val_bits - 1)) and "over" (1 iff bytes_before plus the entry's
+    own length passes ``budgets[g]``; budgets has seg_cap entries).  ``seg_starts`` and ``nseg``
+    are as reduce() takes them.  Returns (rank u32[n], bytes_before u64[n], sum_before u64[n],
+    over u8[n], code), None where not wanted; positions that no segment covers hold 0.  code is 0
+    or errno.EINVAL for a table that decreases or ends past the list."""
+    index = np.ascontiguousarray(index, dtype=np.uint32)
+    seg_starts = np.ascontiguousarray(seg_starts, dtype=np.uint64)
+    cap = max(len(seg_starts) - 1, 0)
+    n = len(index)
+    if ret is not None:
+        ret = np.ascontiguousarray(ret, dtype=np.uint64)
+    if count is None:
+        count = 0 if ret is None else len(ret)
+    offs = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
+    if budgets is not None:
+        budgets = np.ascontiguousarray(budgets, dtype=np.uint64)
+        assert len(budgets) == cap
+    b = None
+    if "bytes_before" in want or "over" in want:   # (data: never read)
+        b = PktBatch(1 if count else None, None if offs is None else offs.ctypes.data, count,
+                     stride, BATCH_EXTENTS if extents else 0)
+    outs = [np.zeros(n, dtype=_SCAN_TYPES[name]) if name in want else None for name in SCANS]
+    scans = BatchScans(*[None if o is None else o.ctypes.data or 1 for o in outs])
+    ns = None if nseg is None else np.array([nseg], dtype=np.uint64)
+    code = lib().ebpf_batch_scan(None if b is None else ctypes.byref(b),
+                                 None if ret is None else ret.ctypes.data or 1,
+                                 count, val_shift, val_bits, index.ctypes.data if n else None, n,
+                                 seg_starts.ctypes.data if len(seg_starts) else None, cap,
+                                 None if ns is None else ns.ctypes.data,
+                                 None if budgets is None else budgets.ctypes.data or 1,
+                                 ctypes.byref(scans))
+    if code not in (0, errno.EINVAL):
+        raise EbpfError(code, "ebpf_batch_scan")
+    return (*outs, code)
+
+
+def scan_dev(device, ret_ptr, count, val_shift, val_bits, index_ptr, n, seg_starts_ptr, seg_cap,
+             nseg_ptr=None, budgets_ptr=None, rank_ptr=None, bytes_before_ptr=None,
+             sum_before_ptr=None, over_ptr=None, stride=0, offsets_ptr=None, extents=False,
+             data_ptr=None, stream=None):
+    """ebpf_batch_scan_dev: device pointers (ints); the outputs that are wanted are given, each n
+    entries (rank u32, bytes_before and sum_before u64, over u8).  The batch (count, stride,
+    offsets_ptr, extents) as run_batch_dev takes it is needed for ``bytes_before_ptr`` and
+    ``over_ptr`` alone, ``budgets_ptr`` (seg_cap u64) for ``over_ptr``; ``data_ptr`` is never read
+    (None: a stand-in).  Asynchronous on ``stream``."""
+    b = None
+    if bytes_before_ptr is not None or over_ptr is not None:
+        b = PktBatch(data_ptr or (1 if count else None), offsets_ptr, count, stride,
+                     BATCH_EXTENTS if extents else 0)
+    scans = BatchScans(rank_ptr, bytes_before_ptr, sum_before_ptr, over_ptr)
+    _check(lib().ebpf_batch_scan_dev(device, None if b is None else ctypes.byref(b), ret_ptr,
+                                     count, val_shift, val_bits, index_ptr, n, seg_starts_ptr,
+                                     seg_cap, nseg_ptr, budgets_ptr, ctypes.byref(scans), stream),
+           "ebpf_batch_scan_dev")
 
 
 def gather(data, count, index, out_stride=0, stride=0, offsets=None, extents=False,

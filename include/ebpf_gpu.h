@@ -489,6 +489,88 @@ int ebpf_batch_reduce_dev(int device, const struct ebpf_pkt_batch *batch, const 
 			  uint64_t seg_cap, const uint64_t *nseg_dev,
 			  const struct ebpf_batch_sums *out, void *stream);
 
+/* Running totals per segment: where a packet stands inside its group.  The per-position
+ * counterpart of the reduce: for every position of the list, how many entries of its segment came
+ * before it, how many bytes they carried and what their values add up to, in list order (a
+ * grouped index keeps a flow's packets in arrival order), and whether the entry passes a byte
+ * budget of its segment.  A byte quota per flow or backend with tail drop in arrival order, "the
+ * first K packets of every flow", a running sequence offset:
+ *
+ *   ebpf_batch_group_dev(dev, ret, faults, batch.count, 0, 32, index, cap, keys, starts, info,
+ *                        tmp, tmp_bytes, s);
+ *   scans = {rank, NULL, NULL, over};                              (batch.count entries each)
+ *   ebpf_batch_scan_dev(dev, &batch, NULL, batch.count, 0, 0, index, batch.count, starts, cap,
+ *                       info, budgets, &scans, s);
+ *   (packet index[j] is within its flow's quota iff over[j] == 0; rank[j] < K samples a flow)
+ *
+ * List, segments and R: exactly as for ebpf_batch_reduce.  index[0 .. n) is any list of packets
+ *   of the batch; segment g is index[seg_starts[g] .. seg_starts[g + 1]); R is seg_cap when nseg is
+ *   NULL, else *nseg when *nseg <= seg_cap, else seg_cap - 1 (0 for seg_cap == 0).
+ *   ebpf_batch_group_dev's group_starts, group_cap and info (as nseg) plug in as they stand, after
+ *   it on the same stream; so does a steering table.  seg_starts[0 .. R] is read: it is
+ *   non-decreasing and seg_starts[R] <= n.
+ * Per position j of segment g (seg_starts[g] <= j < seg_starts[g + 1], g < R), with i = index[j],
+ *   len_j and the value as the reduce has them (the length 0 for an end below the start, for an
+ *   end 2^32 bytes or more past it and for i >= count; the value (ret[i] >> val_shift) &
+ *   (2^val_bits - 1), and an entry with i >= count has none and adds 0):
+ *     rank[j]         = j - seg_starts[g]: the entries of the segment before this one;
+ *     bytes_before[j] = the sum of their lengths;
+ *     sum_before[j]   = the sum of their values, modulo 2^64;
+ *     over[j]         = 1 iff bytes_before[j] + len_j > budgets[g], else 0 (the sum cannot wrap: at
+ *                       most 2^32 entries of less than 2^32 bytes each).
+ *   budgets has seg_cap entries, of which [0, R) are read.  So for the last position of a segment
+ *   bytes_before + len_j is the reduce's bytes[g], and the same for sum.  faults is not consulted.
+ * Positions that no segment covers, those before seg_starts[0] and those at or past seg_starts[R]
+ *   (the faulted tail of a grouped index; every position when R == 0): every wanted output is 0
+ *   there.  So every wanted output is written in full, [0, n), and nothing at or past entry n is.
+ * Outputs (struct ebpf_batch_scans): each member is NULL (not wanted: it costs nothing) or has n
+ *   entries, by list position.
+ * Which arguments may be NULL: batch iff bytes_before and over both are; ret iff sum_before is;
+ *   budgets iff over is; with all four outputs NULL the call succeeds and does nothing.
+ *   batch->data is never read, and of batch->offsets only the listed packets' entries.
+ * The output is a function of the inputs alone: it does not depend on what the output arrays held
+ * on entry, and two calls on the same input give the same bytes.
+ *
+ * ebpf_batch_scan: host buffers, a plain loop; no GPU needed (the statement of what the device
+ *   function computes).  It also returns EINVAL, with nothing written, when seg_starts[0 .. R] is
+ *   not non-decreasing or seg_starts[R] > n.
+ * ebpf_batch_scan_dev: every pointer (batch->offsets, ret_dev, index_dev, seg_starts_dev,
+ *   nseg_dev, budgets_dev and the members of *out; batch and out themselves are host structs) is
+ *   device memory on `device`; enqueued on `stream` (hipStream_t, NULL = default stream), returns
+ *   without synchronising and never waits for the device.  It cannot look at the table: for one
+ *   that is not non-decreasing or that ends past n the outputs are unspecified, but nothing
+ *   outside index[0 .. n), ret[0 .. count), the listed packets' offsets entries, seg_starts[0 .. R]
+ *   and budgets[0 .. R) is read, and nothing outside the outputs' [0, n) is written.  The cost
+ *   follows the list's length, not the shape of the segments; a budget is fetched once per segment
+ *   and tile of 4,096 positions that the segment touches, not per position.  Temporary storage
+ *   is the library's, per stream, shared with ebpf_batch_steer_dev, ebpf_batch_group_dev and
+ *   ebpf_batch_reduce_dev: 72 bytes per 4,096 list entries (none for rank alone).  The outputs
+ *   may not overlap the inputs or each other.  ret_dev, seg_starts_dev, nseg_dev, budgets_dev,
+ *   batch->offsets, bytes_before and sum_before must be 8-byte aligned, index_dev and rank 4-byte
+ *   aligned, as their types say; over may have any alignment.
+ * Both return 0; EINVAL for a NULL out, for val_bits outside [1, 64] or val_shift + val_bits > 64
+ * when sum_before is wanted, a NULL ret, batch or budgets where an output needs it, a batch that
+ * the run functions would refuse, batch->count != count when batch is given, a NULL index with
+ * n > 0, a NULL seg_starts with seg_cap > 0; then E2BIG for n, count or seg_cap above 0xffffffff.
+ * All of these are known on the host, before the device is looked at.  The device function then
+ * returns ENODEV (no GPU, or no such device), ENOMEM (no scratch) or EIO.  Neither changes the
+ * calling thread's current HIP device. */
+struct ebpf_batch_scans {      /* each NULL (not wanted: it costs nothing) or n entries, by list position */
+	uint32_t *rank;         /* entries of the same segment before this one */
+	uint64_t *bytes_before; /* sum of their lengths */
+	uint64_t *sum_before;   /* sum of their values, modulo 2^64 */
+	uint8_t  *over;         /* 1 iff bytes_before + own length > the segment's budget */
+};
+int ebpf_batch_scan(const struct ebpf_pkt_batch *batch, const uint64_t *ret, uint64_t count,
+		    uint32_t val_shift, uint32_t val_bits, const uint32_t *index, uint64_t n,
+		    const uint64_t *seg_starts, uint64_t seg_cap, const uint64_t *nseg,
+		    const uint64_t *budgets, const struct ebpf_batch_scans *out);
+int ebpf_batch_scan_dev(int device, const struct ebpf_pkt_batch *batch, const uint64_t *ret_dev,
+			uint64_t count, uint32_t val_shift, uint32_t val_bits,
+			const uint32_t *index_dev, uint64_t n, const uint64_t *seg_starts_dev,
+			uint64_t seg_cap, const uint64_t *nseg_dev, const uint64_t *budgets_dev,
+			const struct ebpf_batch_scans *out, void *stream);
+
 /* Gathering packets into a dense batch: a list of n packets of `batch` (a class of a steered
  * batch, the whole steering index, any list of the caller's own: duplicates and any order are
  * fine) copied, in list order, into `out`.  A class can then leave the device on its own (a TX
