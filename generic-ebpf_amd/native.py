@@ -78,6 +78,21 @@ class BatchScans(ctypes.Structure):
                 ("sum_before", ctypes.c_void_p), ("over", ctypes.c_void_p)]
 
 
+class BatchTest(ctypes.Structure):
+    """struct ebpf_batch_test: the tests of a filter call, a conjunction; a NULL member is none"""
+    _fields_ = [("flags", ctypes.c_void_p), ("rank", ctypes.c_void_p),
+                ("rank_below", ctypes.c_uint32), ("ret", ctypes.c_void_p),
+                ("val_shift", ctypes.c_uint32), ("val_bits", ctypes.c_uint32),
+                ("val_lo", ctypes.c_uint64), ("val_hi", ctypes.c_uint64)]
+
+
+class BatchParts(ctypes.Structure):
+    """struct ebpf_batch_parts: the outputs of a filter call, each NULL or n (the lists) or
+    seg_cap + 1 (their tables) entries"""
+    _fields_ = [("kept", ctypes.c_void_p), ("kept_starts", ctypes.c_void_p),
+                ("dropped", ctypes.c_void_p), ("dropped_starts", ctypes.c_void_p)]
+
+
 class BatchStats(ctypes.Structure):
     _fields_ = [("packets", ctypes.c_uint64), ("faulted", ctypes.c_uint64),
                 ("hist", ctypes.c_uint64 * EBPF_HIST_BINS), ("kernel_ms", ctypes.c_double),
@@ -149,6 +164,8 @@ FUNCS = {
     "ebpf_batch_scan": (_I, [_VP, _VP, _U64, _U32, _U32, _VP, _U64, _VP, _U64, _VP, _VP, _VP]),
     "ebpf_batch_scan_dev": (_I, [_I, _VP, _VP, _U64, _U32, _U32, _VP, _U64, _VP, _U64, _VP, _VP, _VP,
                                  _VP]),
+    "ebpf_batch_filter": (_I, [_VP, _U64, _VP, _U64, _VP, _U64, _VP, _VP, _VP]),
+    "ebpf_batch_filter_dev": (_I, [_I, _VP, _U64, _VP, _U64, _VP, _U64, _VP, _VP, _VP, _VP]),
     "ebpf_batch_gather": (_I, [_VP, _VP, _U64, _U32, _VP, _U64, _VP]),
     "ebpf_batch_gather_dev": (_I, [_I, _VP, _VP, _U64, _U32, _VP, _U64, _VP, _VP]),
     "ebpf_batch_scatter": (_I, [_VP, _VP, _U64, _U32, _VP, _U64, _VP]),
@@ -165,6 +182,7 @@ _lib = None
 BATCH_HIST_OVERWRITE = 0x1  # include/ebpf_gpu.h EBPF_BATCH_HIST_OVERWRITE
 BATCH_EXTENTS = 0x2         # EBPF_BATCH_EXTENTS: offsets holds (start, end) pairs
 STEER_STARTS = EBPF_HIST_BINS + 1  # EBPF_STEER_STARTS: entries of a steering call's starts
+EBPF_NO_PACKET = 0xffffffff  # EBPF_NO_PACKET: a list entry that names no packet
 STEER_TILE = 4096           # csrc/host/steer.h STEER_TILE: packets per workgroup of the kernels
 
 
@@ -755,6 +773,72 @@ def scan_dev(device, ret_ptr, count, val_shift, val_bits, index_ptr, n, seg_star
                                      count, val_shift, val_bits, index_ptr, n, seg_starts_ptr,
                                      seg_cap, nseg_ptr, budgets_ptr, ctypes.byref(scans), stream),
            "ebpf_batch_scan_dev")
+
+
+PARTS = ("kept", "kept_starts", "dropped", "dropped_starts")   # struct ebpf_batch_parts' members
+
+
+def filter(index, seg_starts=None, flags=None, rank=None, rank_below=0, ret=None, val_shift=0,
+           val_bits=64, val_lo=0, val_hi=(1 << 64) - 1, count=None, nseg=None, want=PARTS):
+    """ebpf_batch_filter on host arrays: the entries of the list whose position passes every test
+    that is given — ``flags[j] == 0``, ``rank[j] < rank_below``, and val_lo <= (ret[index[j]] >>
+    val_shift) & (2**val_bits - 1) <= val_hi — in list order, and those that fail, with the tables
+    of the segments they inherit.  ``seg_starts`` and ``nseg`` are as reduce() takes them;
+    ``seg_starts`` None is an unsegmented list (no tables then).  Returns (kept u32[n],
+    kept_starts u64[seg_cap + 1], dropped u32[n], dropped_starts u64[seg_cap + 1], info u64[2] =
+    (kept, dropped), code), None where not wanted (``want`` names them); the lists' tails hold
+    EBPF_NO_PACKET, table entries past the segments 0.  code is 0 or errno.EINVAL for a table that
+    decreases or ends past the list."""
+    index = np.ascontiguousarray(index, dtype=np.uint32)
+    n = len(index)
+    if seg_starts is not None:
+        seg_starts = np.ascontiguousarray(seg_starts, dtype=np.uint64)
+        assert len(seg_starts) >= 1
+    cap = 0 if seg_starts is None else len(seg_starts) - 1
+    if flags is not None:
+        flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        assert len(flags) == n
+    if rank is not None:
+        rank = np.ascontiguousarray(rank, dtype=np.uint32)
+        assert len(rank) == n
+    if ret is not None:
+        ret = np.ascontiguousarray(ret, dtype=np.uint64)
+    if count is None:
+        count = 0 if ret is None else len(ret)
+    test = BatchTest(None if flags is None else flags.ctypes.data or 1,
+                     None if rank is None else rank.ctypes.data or 1, rank_below,
+                     None if ret is None else ret.ctypes.data or 1, val_shift, val_bits,
+                     val_lo, val_hi)
+    if seg_starts is None:
+        want = [k for k in want if not k.endswith("_starts")]
+    outs = [(np.zeros(cap + 1 if k.endswith("_starts") else n,
+                      dtype=np.uint64 if k.endswith("_starts") else np.uint32)
+             if k in want else None) for k in PARTS]
+    parts = BatchParts(*[None if o is None else o.ctypes.data or 1 for o in outs])
+    info = np.zeros(2, dtype=np.uint64)
+    ns = None if nseg is None else np.array([nseg], dtype=np.uint64)
+    code = lib().ebpf_batch_filter(ctypes.byref(test), count, index.ctypes.data if n else None, n,
+                                   None if seg_starts is None else seg_starts.ctypes.data, cap,
+                                   None if ns is None else ns.ctypes.data, ctypes.byref(parts),
+                                   info.ctypes.data)
+    if code not in (0, errno.EINVAL):
+        raise EbpfError(code, "ebpf_batch_filter")
+    return (*outs, info, code)
+
+
+def filter_dev(device, count, index_ptr, n, seg_starts_ptr, seg_cap, info_ptr, nseg_ptr=None,
+               flags_ptr=None, rank_ptr=None, rank_below=0, ret_ptr=None, val_shift=0,
+               val_bits=64, val_lo=0, val_hi=(1 << 64) - 1, kept_ptr=None, kept_starts_ptr=None,
+               dropped_ptr=None, dropped_starts_ptr=None, stream=None):
+    """ebpf_batch_filter_dev: device pointers (ints); the tests that are given apply, the outputs
+    that are wanted are given (kept and dropped n u32, their tables seg_cap + 1 u64);
+    ``info_ptr`` (2 u64) gets the numbers kept and dropped.  ``seg_starts_ptr`` None: an
+    unsegmented list.  Asynchronous on ``stream``."""
+    test = BatchTest(flags_ptr, rank_ptr, rank_below, ret_ptr, val_shift, val_bits, val_lo, val_hi)
+    parts = BatchParts(kept_ptr, kept_starts_ptr, dropped_ptr, dropped_starts_ptr)
+    _check(lib().ebpf_batch_filter_dev(device, ctypes.byref(test), count, index_ptr, n,
+                                       seg_starts_ptr, seg_cap, nseg_ptr, ctypes.byref(parts),
+                                       info_ptr, stream), "ebpf_batch_filter_dev")
 
 
 def gather(data, count, index, out_stride=0, stride=0, offsets=None, extents=False,

@@ -571,6 +571,110 @@ int ebpf_batch_scan_dev(int device, const struct ebpf_pkt_batch *batch, const ui
 			uint64_t seg_cap, const uint64_t *nseg_dev, const uint64_t *budgets_dev,
 			const struct ebpf_batch_scans *out, void *stream);
 
+/* Keeping part of a list: a stable compaction that carries the segments along.  The scan leaves
+ * flags and ranks per list position; this turns them, or a bit field of the verdicts, into lists
+ * that every other list function takes — the entries that pass a test (kept) and those that do
+ * not (dropped), each in list order, each with a table of its own — with nothing per packet read
+ * on the host.  A byte quota per flow, what passed forwarded and what was dropped counted per flow:
+ *
+ *   scans = {rank, NULL, NULL, over};
+ *   ebpf_batch_scan_dev(dev, &batch, NULL, batch.count, 0, 0, index, batch.count, starts, cap,
+ *                       info, budgets, &scans, s);
+ *   test = {over, NULL, 0, NULL, 0, 0, 0, 0};       (test = {NULL, rank, K, ...}: K packets a flow)
+ *   parts = {kept, kept_starts, dropped, dropped_starts};
+ *   ebpf_batch_filter_dev(dev, &test, batch.count, index, batch.count, starts, cap, info, &parts,
+ *                         kd, s);
+ *   ebpf_batch_gather_dev(dev, &batch, kept, batch.count, 64, out, ...);   (slots past kd[0]: zeros)
+ *   sums = {bytes, NULL, NULL, NULL, NULL};
+ *   ebpf_batch_reduce_dev(dev, &batch, NULL, batch.count, 0, 0, dropped, batch.count,
+ *                         dropped_starts, cap, info, &sums, s);
+ *
+ * List, segments and R: exactly as for ebpf_batch_reduce and ebpf_batch_scan.  index[0 .. n) is any
+ *   list of packets of the batch; R is seg_cap when nseg is NULL, else *nseg when *nseg <= seg_cap,
+ *   else seg_cap - 1 (0 for seg_cap == 0).  ebpf_batch_group_dev's group_starts, group_cap and info
+ *   (as nseg) plug in as they stand, after it on the same stream; so does a steering table.
+ *   seg_starts[0 .. R] is read: it is non-decreasing and seg_starts[R] <= n.  A position j takes
+ *   part iff a segment covers it: seg_starts[0] <= j < min(seg_starts[R], n); with R == 0 (a
+ *   non-NULL seg_starts with seg_cap == 0 included) nothing takes part.
+ *   seg_starts == NULL is an unsegmented list: it needs seg_cap == 0 and nseg == NULL, every
+ *   position of [0, n) takes part, and kept_starts and dropped_starts must be NULL.
+ * Test (struct ebpf_batch_test): a conjunction; a NULL member is no test.  A position j that takes
+ *   part passes iff every given member's test holds, with i = index[j]:
+ *     flags (n entries, by list position):  flags[j] == 0;
+ *     rank  (n entries, by list position):  rank[j] < rank_below;
+ *     ret   (count entries, by packet):     i < count and val_lo <= v <= val_hi as unsigned
+ *           numbers, v = (ret[i] >> val_shift) & (2^val_bits - 1), 1 <= val_bits <= 64 and
+ *           val_shift + val_bits <= 64.  An entry with i >= count has no value: it fails.
+ *           val_lo > val_hi is legal: nothing passes.
+ *   With all three NULL every position that takes part passes.  faults is not consulted.
+ * Outputs (struct ebpf_batch_parts): each member is NULL (not wanted: it costs nothing).  Let K be
+ *   the number of positions that take part and pass, D the number that take part and fail.
+ *     info[0] = K, info[1] = D: 2 entries, always written.
+ *     kept[0 .. K) = index[j] of the passing positions, in list order (a stable compaction);
+ *       kept[K .. n) = EBPF_NO_PACKET.  n entries, written in full, as the group's index is:
+ *       every list function treats an entry >= count as a packet of length 0 that has no value
+ *       and is never written to, so (kept, n) is a list as it stands.
+ *     dropped[0 .. D) likewise of the failing positions; dropped[D .. n) = EBPF_NO_PACKET.
+ *     kept_starts[g], for g <= R = the number of passing positions j with
+ *       seg_starts[0] <= j < min(seg_starts[g], n).  So kept_starts[0] = 0, kept_starts[R] = K, and
+ *       segment g of the kept list is kept[kept_starts[g] .. kept_starts[g + 1]), maybe empty:
+ *       (kept, n, kept_starts, seg_cap, nseg) is a list with a table for ebpf_batch_reduce_dev and
+ *       ebpf_batch_scan_dev, after this call on the same stream with the same seg_cap and nseg.
+ *       seg_cap + 1 entries, of which [0 .. R] are written; entries past R are not.
+ *     dropped_starts[g] likewise of the failing positions; dropped_starts[R] = D.
+ *   With all four NULL only info is written (a count).  n == 0 succeeds: info = {0, 0} and the
+ *   tables' [0 .. R] are 0.
+ * The output is a function of the inputs alone: it does not depend on what the outputs held on
+ * entry, and two calls on the same input give the same bytes.  The outputs may not overlap the
+ * inputs or each other.
+ *
+ * ebpf_batch_filter: host buffers, a plain loop; no GPU needed (the statement of what the device
+ *   function computes).  It also returns EINVAL, with nothing written, when seg_starts[0 .. R] is
+ *   not non-decreasing or seg_starts[R] > n.
+ * ebpf_batch_filter_dev: every pointer (the members of *test and *out, index_dev, seg_starts_dev,
+ *   nseg_dev and info_dev; test and out themselves are host structs) is device memory on
+ *   `device`; enqueued on `stream` (hipStream_t, NULL = default stream), returns without
+ *   synchronising and never waits for the device.  It cannot look at the table: for one that is
+ *   not non-decreasing or that ends past n the outputs are unspecified, but every position is
+ *   clamped: nothing outside flags[0 .. n), rank[0 .. n), index[0 .. n), ret[0 .. count) and
+ *   seg_starts[0 .. R] is read, and nothing outside kept[0 .. n), dropped[0 .. n), the tables'
+ *   [0 .. R] and info[0 .. 2) is written.  The cost follows the list's length and the table's, not
+ *   the shape of the segments or how many entries pass.  Temporary storage is the library's, per
+ *   stream, shared with ebpf_batch_steer_dev, ebpf_batch_group_dev, ebpf_batch_reduce_dev and
+ *   ebpf_batch_scan_dev: 516 bytes per 4,096 list entries (a bit per position and a count per
+ *   tile) and 16 bytes a call.  rank, index_dev, kept and dropped must be 4-byte aligned, ret,
+ *   seg_starts_dev, nseg_dev, info_dev and the tables 8-byte aligned, as their types say; flags may
+ *   have any alignment.
+ * Both return 0; EINVAL for a NULL test, out or info, for val_bits outside [1, 64] or val_shift +
+ * val_bits > 64 when test->ret is given, a NULL index with n > 0, a NULL seg_starts with
+ * seg_cap > 0 or with nseg given, kept_starts or dropped_starts given with a NULL seg_starts; then
+ * E2BIG for n, count or seg_cap above 0xffffffff.  All of these are known on the host, before the
+ * device is looked at.  The device function then returns ENODEV (no GPU, or no such device),
+ * ENOMEM (no scratch) or EIO.  Neither changes the calling thread's current HIP device. */
+#define EBPF_NO_PACKET 0xffffffffu  /* a list entry that names no packet: >= any count */
+
+struct ebpf_batch_test {      /* a conjunction; a NULL member is no test */
+	const uint8_t  *flags;    /* n entries by list position: passes iff flags[j] == 0        */
+	const uint32_t *rank;     /* n entries by list position: passes iff rank[j] < rank_below */
+	uint32_t        rank_below;
+	const uint64_t *ret;      /* count entries by packet: passes iff index[j] < count and    */
+	uint32_t        val_shift, val_bits;   /* val_lo <= (ret[i] >> val_shift) & mask <= val_hi */
+	uint64_t        val_lo, val_hi;
+};
+struct ebpf_batch_parts {     /* each NULL (not wanted: it costs nothing) */
+	uint32_t *kept;           /* n entries, written in full */
+	uint64_t *kept_starts;    /* seg_cap + 1 entries, [0 .. R] written */
+	uint32_t *dropped;        /* n entries, written in full */
+	uint64_t *dropped_starts; /* seg_cap + 1 entries, [0 .. R] written */
+};
+int ebpf_batch_filter(const struct ebpf_batch_test *test, uint64_t count, const uint32_t *index,
+		      uint64_t n, const uint64_t *seg_starts, uint64_t seg_cap, const uint64_t *nseg,
+		      const struct ebpf_batch_parts *out, uint64_t *info);
+int ebpf_batch_filter_dev(int device, const struct ebpf_batch_test *test, uint64_t count,
+			  const uint32_t *index_dev, uint64_t n, const uint64_t *seg_starts_dev,
+			  uint64_t seg_cap, const uint64_t *nseg_dev,
+			  const struct ebpf_batch_parts *out, uint64_t *info_dev, void *stream);
+
 /* Gathering packets into a dense batch: a list of n packets of `batch` (a class of a steered
  * batch, the whole steering index, any list of the caller's own: duplicates and any order are
  * fine) copied, in list order, into `out`.  A class can then leave the device on its own (a TX
