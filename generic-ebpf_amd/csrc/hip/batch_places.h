@@ -1,10 +1,12 @@
-// batch_places.h — what gather.hip, scatter.hip, reduce.hip and scan.hip share: where a batch
-// keeps its packets, the length rule, a workgroup's scan, the 16-byte load / store forms, and what
-// the segmented kernels need of a list's segments (their number, the 64-way search, a tile's LDS
-// slots, a thread's lengths and values).  Device code only; every file that includes it is compiled
-// on its own, so everything here is file-local.
+// batch_places.h — what the list kernels share: where a batch keeps its packets and the length
+// rule (gather.hip, scatter.hip, and through seg_tile.h reduce.hip and scan.hip), a workgroup's
+// scan (those four and filter.hip), and the 16-byte load / store forms (gather.hip, scatter.hip,
+// scan.hip, filter.hip).  What only the segmented kernels need is in seg_tile.h.  Device code only;
+// every file that includes it is compiled on its own, so everything here is file-local.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "ebpf_gpu.h"
 
@@ -84,114 +86,34 @@ lens_of(const places &f, const uint32_t *__restrict__ index, uint64_t n, uint64_
 	}
 }
 
-// The sum of v over the threads before this one; total = over them all.  wsum: WAVES words of
-// LDS, free again on return.
-__device__ __forceinline__ uint64_t
-block_scan(uint64_t v, uint64_t *wsum, uint64_t &total)
+// The sum of v over the threads before this one, of a workgroup of NW waves; total = over them
+// all.  wsum: NW words of LDS, free again on return.  T, uint32_t or uint64_t, is wsum's: v
+// converts to it.
+template <uint32_t NW = WAVES, typename T>
+__device__ __forceinline__ T
+block_scan(std::common_type_t<T> v, T *wsum, T &total)
 {
 	const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-	uint64_t inc = v; // inclusive scan over the wave
+	T inc = v; // inclusive scan over the wave
 #pragma unroll
 	for (uint32_t d = 1; d < 64; d <<= 1) {
-		const uint64_t up = __shfl_up((unsigned long long)inc, d);
+		const T up = __shfl_up(inc, d);
 		if (lane >= d)
 			inc += up;
 	}
 	if (lane == 63)
 		wsum[w] = inc;
 	__syncthreads();
-	uint64_t before = 0, all = 0;
+	T before = 0, all = 0;
 #pragma unroll
-	for (uint32_t q = 0; q < WAVES; q++) {
-		const uint64_t s = wsum[q];
+	for (uint32_t q = 0; q < NW; q++) {
+		const T s = wsum[q];
 		before += q < w ? s : 0;
 		all += s;
 	}
 	__syncthreads();
 	total = all;
 	return before + inc - v;
-}
-
-// The number of segments of a list (ebpf_gpu.h): a short table holds no end for its last group.
-__device__ __forceinline__ uint64_t
-segments_of(uint64_t cap, const uint64_t *__restrict__ nseg)
-{
-	if (nseg == nullptr)
-		return cap;
-	const uint64_t g = *nseg;
-	return g <= cap ? g : (cap != 0 ? cap - 1 : 0);
-}
-
-// How many of S[0 .. m) are <= p, for a non-decreasing S: a wave's 64-way search, every lane the
-// same answer.  For any other S it still ends, with an answer in [0, m], having read only S[0 .. m).
-__device__ __forceinline__ uint64_t
-upper(const uint64_t *__restrict__ S, uint64_t m, uint64_t p)
-{
-	const uint32_t lane = threadIdx.x & 63;
-	uint64_t lo = 0, hi = m;
-	while (lo < hi) {
-		const uint64_t step = (hi - lo + 63) / 64;
-		const uint64_t at = lo + lane * step;
-		const bool le = at < hi && S[at] <= p;
-		const uint64_t b = ~__ballot(le);
-		const uint32_t c = b == 0 ? 64u : (uint32_t)__builtin_ctzll(b); // the probes <= p, from lo on
-		if (c == 0)
-			break;
-		const uint64_t end = lo + c * step;
-		lo += (c - 1) * step + 1;
-		hi = end < hi ? end : hi;
-	}
-	return lo;
-}
-
-// Where position q of a tile sits in LDS: a thread's 16 positions are a row, and a word of
-// padding a row keeps both the tile-order and the row-order accesses off one another's banks.
-__device__ __forceinline__ uint32_t
-slot(uint32_t q)
-{
-	return q + (q >> 4);
-}
-
-// A thread's N list entries idx[k]: their lengths (0 where !has[k]: past the list's end, or past
-// the batch's) and their value fields of ret (ret has f.count >= 1 entries; an entry past the
-// batch reads the last one, and its value is not used).  The ret loads are issued together, then
-// the offsets loads, as lens_of's.
-template <bool LENS, bool VALS, uint32_t N>
-__device__ __forceinline__ void
-fields_of(const places &f, const uint64_t *__restrict__ ret, uint32_t val_shift, uint64_t val_mask,
-	  const uint32_t (&idx)[N], const bool (&has)[N], uint32_t (&len)[N], uint64_t (&val)[N])
-{
-	uint64_t s[N], e[N];
-	if (VALS) {
-#pragma unroll
-		for (uint32_t k = 0; k < N; k++)
-			val[k] = ret[idx[k] < f.count ? idx[k] : f.count - 1];
-#pragma unroll
-		for (uint32_t k = 0; k < N; k++)
-			val[k] = (val[k] >> val_shift) & val_mask;
-	}
-	if (LENS) {
-#pragma unroll
-		for (uint32_t k = 0; k < N; k++) {
-			s[k] = e[k] = 0;
-			if (!has[k])
-				continue;
-			if (f.offsets == nullptr) {
-				e[k] = f.stride;
-			} else if (f.extents) {
-				s[k] = f.offsets[2 * (uint64_t)idx[k]];
-				e[k] = f.offsets[2 * (uint64_t)idx[k] + 1];
-			} else {
-				s[k] = f.offsets[idx[k]];
-				e[k] = f.offsets[(uint64_t)idx[k] + 1];
-			}
-		}
-#pragma unroll
-		for (uint32_t k = 0; k < N; k++) {
-			const uint64_t d = e[k] - s[k];
-			len[k] = (e[k] < s[k] || (d >> 32) != 0) ? 0u : (uint32_t)d;
-		}
-	}
 }
 
 // 16 bytes at a 16-byte-aligned address

@@ -28,17 +28,12 @@
 #include <hip/hip_runtime.h>
 
 #include "ebpf_gpu.h"
-#include "hip/batch_places.h"
+#include "hip/seg_tile.h"
 #include "host/filter.h"
-#include "host/steer.h"
 
 namespace {
 
-constexpr uint32_t TILE = STEER_TILE;
-constexpr uint32_t PER_THREAD = TILE / THREADS;
-constexpr uint32_t CARRY_THREADS = 1024; // filter_carry's one workgroup
 constexpr uint32_t BITS_WORDS = TILE / 32;
-static_assert(PER_THREAD == 16, "a thread's positions are 16 bits of the tile's");
 static_assert(FILTER_TILE_WORDS == 1 + BITS_WORDS, "a count and a bit per position");
 
 typedef struct ebpf_batch_test tests;
@@ -58,10 +53,8 @@ cover_of(const uint64_t *__restrict__ S, uint64_t cap, const uint64_t *__restric
 	const uint64_t R = segments_of(cap, nseg);
 	if (R == 0)
 		return {0, 0, 0};
-	uint64_t a = S[0], b = S[R];
-	b = b < n ? b : n;
-	a = a < b ? a : b;
-	return {a, b, R};
+	const uint64_t a = S[0], b = seg_end(S, R, n);
+	return {a < b ? a : b, b, R};
 }
 
 __device__ __forceinline__ uint64_t
@@ -159,7 +152,7 @@ filter_tiles(tests t, uint64_t val_mask, uint64_t count, const uint32_t *__restr
 		if (VAL && count != 0) {
 #pragma unroll
 			for (uint32_t k = 0; k < PER_THREAD; k++) {
-				const uint64_t f = (v[k] >> t.val_shift) & val_mask;
+				const uint64_t f = bit_field{t.val_shift, val_mask}.of(v[k]);
 				const bool ok = idx[k] < count && t.val_lo <= f && f <= t.val_hi;
 				pass &= ~((ok ? 0u : 1u) << k);
 			}
@@ -174,46 +167,28 @@ filter_tiles(tests t, uint64_t val_mask, uint64_t count, const uint32_t *__restr
 		counts[blockIdx.x] = (uint32_t)total;
 }
 
-// One workgroup: thread s walks tiles [s * seglen, (s + 1) * seglen) twice, first for its run's
-// total, then, with the totals of the threads before it, to leave in every tile's word the
-// passing positions of the tiles before.  K <= n < 2^32: 32-bit sums.
+// One workgroup: a thread walks its run of tiles (run_of) twice, first for its run's total, then,
+// with the totals of the threads before it, to leave in every tile's word the passing positions
+// of the tiles before.  K <= n < 2^32: 32-bit sums.
 __global__ void __launch_bounds__(CARRY_THREADS)
 filter_carry(uint32_t *__restrict__ scratch, uint32_t ntiles, uint64_t n,
 	     const uint64_t *__restrict__ S, uint64_t cap, const uint64_t *__restrict__ nseg,
 	     uint64_t *__restrict__ info)
 {
 	__shared__ uint32_t wsum[CARRY_THREADS / 64];
-	const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
 	uint32_t *counts = scratch + FILTER_HEAD_WORDS;
-	const uint32_t seglen = (ntiles + CARRY_THREADS - 1) / CARRY_THREADS;
-	const uint32_t t0 = min(tid * seglen, ntiles), t1 = min(t0 + seglen, ntiles);
+	const auto [t0, t1] = run_of(ntiles);
 	uint32_t mine = 0;
 	for (uint32_t t = t0; t < t1; t++)
 		mine += counts[t];
-	uint32_t inc = mine; // inclusive scan over the wave
-#pragma unroll
-	for (uint32_t d = 1; d < 64; d <<= 1) {
-		const uint32_t up = __shfl_up(inc, d);
-		if (lane >= d)
-			inc += up;
-	}
-	if (lane == 63)
-		wsum[w] = inc;
-	__syncthreads();
-	uint32_t before = 0, all = 0;
-#pragma unroll
-	for (uint32_t q = 0; q < CARRY_THREADS / 64; q++) {
-		const uint32_t s = wsum[q];
-		before += q < w ? s : 0;
-		all += s;
-	}
-	uint32_t cur = before + inc - mine;
+	uint32_t all;
+	uint32_t cur = block_scan<CARRY_THREADS / 64>(mine, wsum, all);
 	for (uint32_t t = t0; t < t1; t++) {
 		const uint32_t own = counts[t];
 		counts[t] = cur;
 		cur += own;
 	}
-	if (tid == 0) {
+	if (threadIdx.x == 0) {
 		const cover c = cover_of(S, cap, nseg, n);
 		scratch[0] = all;
 		info[0] = all;
@@ -332,20 +307,6 @@ filter_place(const uint32_t *__restrict__ scratch, uint32_t ntiles,
 	}
 }
 
-template <bool FLAGS, bool RANK>
-void
-launch_tiles(bool val, const tests &t, uint64_t val_mask, uint64_t count, const uint32_t *index,
-	     uint64_t n, const uint64_t *S, uint64_t cap, const uint64_t *nseg, uint32_t *scratch,
-	     uint32_t ntiles, hipStream_t stream)
-{
-	if (val)
-		hipLaunchKernelGGL((filter_tiles<FLAGS, RANK, true>), dim3(ntiles), dim3(THREADS), 0,
-				   stream, t, val_mask, count, index, n, S, cap, nseg, scratch, ntiles);
-	else
-		hipLaunchKernelGGL((filter_tiles<FLAGS, RANK, false>), dim3(ntiles), dim3(THREADS), 0,
-				   stream, t, val_mask, count, index, n, S, cap, nseg, scratch, ntiles);
-}
-
 uint32_t
 tiles_of(uint64_t n)
 {
@@ -368,31 +329,19 @@ launch_filter(const struct ebpf_batch_test &test, uint64_t count, const uint32_t
 {
 	const uint32_t ntiles = tiles_of(n);
 	const bool flags = test.flags != nullptr, rank = test.rank != nullptr, val = test.ret != nullptr;
-	const uint64_t mask = test.val_bits >= 64 ? ~0ull : (1ull << test.val_bits) - 1;
-	if (flags && rank)
-		launch_tiles<true, true>(val, test, mask, count, index, n, seg_starts, seg_cap, nseg,
-					 scratch, ntiles, stream);
-	else if (flags)
-		launch_tiles<true, false>(val, test, mask, count, index, n, seg_starts, seg_cap, nseg,
-					  scratch, ntiles, stream);
-	else if (rank)
-		launch_tiles<false, true>(val, test, mask, count, index, n, seg_starts, seg_cap, nseg,
-					  scratch, ntiles, stream);
-	else
-		launch_tiles<false, false>(val, test, mask, count, index, n, seg_starts, seg_cap, nseg,
-					   scratch, ntiles, stream);
+	const uint64_t mask = field_of(test.val_shift, test.val_bits).mask;
+	with_flags([&](auto F, auto R, auto V) {
+		hipLaunchKernelGGL((filter_tiles<F, R, V>), dim3(ntiles), dim3(THREADS), 0, stream, test, mask,
+				   count, index, n, seg_starts, seg_cap, nseg, scratch, ntiles);
+	}, flags, rank, val);
 	hipLaunchKernelGGL(filter_carry, dim3(1), dim3(CARRY_THREADS), 0, stream, scratch, ntiles, n,
 			   seg_starts, seg_cap, nseg, info);
 	const bool lists = out.kept != nullptr || out.dropped != nullptr;
 	const bool tables = out.kept_starts != nullptr || out.dropped_starts != nullptr;
-	if (lists && tables)
-		hipLaunchKernelGGL((filter_place<true, true>), dim3(ntiles), dim3(THREADS), 0, stream,
-				   scratch, ntiles, index, n, seg_starts, seg_cap, nseg, out);
-	else if (lists)
-		hipLaunchKernelGGL((filter_place<true, false>), dim3(ntiles), dim3(THREADS), 0, stream,
-				   scratch, ntiles, index, n, seg_starts, seg_cap, nseg, out);
-	else if (tables)
-		hipLaunchKernelGGL((filter_place<false, true>), dim3(ntiles), dim3(THREADS), 0, stream,
-				   scratch, ntiles, index, n, seg_starts, seg_cap, nseg, out);
+	with_flags([&](auto L, auto T) {
+		if constexpr (L || T) // (no kernel for neither: nothing is placed)
+			hipLaunchKernelGGL((filter_place<L, T>), dim3(ntiles), dim3(THREADS), 0, stream, scratch,
+					   ntiles, index, n, seg_starts, seg_cap, nseg, out);
+	}, lists, tables);
 	return hipGetLastError();
 }

@@ -22,6 +22,7 @@
 // As in steer.hip no atomic decides a position: the output is a function of the input alone.
 #include <hip/hip_runtime.h>
 
+#include "bit_field.h"
 #include "ebpf_gpu.h"
 #include "hip/wave_rank.h"
 #include "host/group.h"
@@ -41,8 +42,7 @@ template <typename K>
 struct source {
 	const uint64_t *ret;
 	const uint8_t *faults;
-	uint32_t key_shift;
-	uint64_t key_mask;
+	bit_field key;
 	const K *keys;
 	const uint32_t *index;
 };
@@ -60,7 +60,7 @@ load_entries(const source<K> &s, uint64_t count, uint64_t unfaulted, uint64_t fi
 		load_verdicts<FAULTS>(s.ret, s.faults, count, first, step, r, f);
 #pragma unroll
 		for (uint32_t k = 0; k < N; k++) {
-			key[k] = (K)((r[k] >> s.key_shift) & s.key_mask);
+			key[k] = (K)s.key.of(r[k]);
 			idx[k] = (uint32_t)(first + k * step);
 		}
 	} else {
@@ -382,8 +382,7 @@ launch_typed(const uint64_t *ret, const uint8_t *faults, uint64_t count, uint32_
 	uint64_t *starts = reinterpret_cast<uint64_t *>(scratch);
 	uint32_t *rows = scratch + STARTS_WORDS;
 	uint32_t *heads = rows + steer_scratch_words(count);
-	source<K> s = {ret, faults, key_shift, key_bits == 64 ? ~0ull : (1ull << key_bits) - 1, nullptr,
-		       nullptr};
+	source<K> s = {ret, faults, field_of(key_shift, key_bits), nullptr, nullptr};
 	for (uint32_t p = 0; p < plan.passes; p++) {
 		const uint32_t dshift = p * plan.digit_bits;
 		const uint32_t dbits = p + 1 < plan.passes ? plan.digit_bits : key_bits - dshift;

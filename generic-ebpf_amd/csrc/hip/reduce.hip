@@ -27,18 +27,12 @@
 #include <hip/hip_runtime.h>
 
 #include "ebpf_gpu.h"
-#include "hip/batch_places.h"
+#include "hip/seg_tile.h"
 #include "host/reduce.h"
-#include "host/steer.h"
 
 namespace {
 
-constexpr uint32_t TILE = STEER_TILE;
-constexpr uint32_t PER_THREAD = TILE / THREADS;
-constexpr uint32_t NOHEAD = ~0u;         // no segment begins here (a segment's number is below it)
-constexpr uint32_t CARRY_THREADS = 1024; // reduce_carry's one workgroup
 constexpr uint32_t ROW = REDUCE_ROW_WORDS;
-static_assert(PER_THREAD == 16, "a thread's positions are one padded LDS row");
 // A tile that closes this many segments or more writes them out through LDS, STAGE at a time.
 constexpr uint32_t STAGE_MIN = 256;
 constexpr uint32_t STAGE = TILE / 2;
@@ -101,33 +95,6 @@ lane_up(const part &p, uint32_t d)
 		r.bits = __shfl_up((unsigned long long)p.bits, d);
 	}
 	return r;
-}
-
-// The join of the runs of the threads before this one, in thread order.  wtot: a part per wave,
-// in LDS.
-template <bool LENS, bool VALS, uint32_t NW>
-__device__ __forceinline__ part
-carry_in(const part &mine, part *wtot)
-{
-	const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-	part inc = mine; // inclusive scan over the wave
-#pragma unroll
-	for (uint32_t d = 1; d < 64; d <<= 1) {
-		const part up = lane_up<LENS, VALS>(inc, d);
-		if (lane >= d)
-			inc = join<LENS, VALS>(up, inc);
-	}
-	if (lane == 63)
-		wtot[w] = inc;
-	__syncthreads();
-	part before = nothing();
-	for (uint32_t q = 0; q < NW; q++) {
-		const part s = wtot[q];
-		if (q < w)
-			before = join<LENS, VALS>(before, s);
-	}
-	const part prev = lane_up<LENS, VALS>(inc, 1);
-	return lane == 0 ? before : join<LENS, VALS>(before, prev);
 }
 
 template <bool LENS, bool VALS>
@@ -239,7 +206,8 @@ write_staged(uint64_t *__restrict__ dst, uint64_t R, const uint32_t (&seg)[PER_T
 
 // rows: per tile, {bytes, sum, min, max, bits, does a segment begin in the tile} over the
 // positions before the first that begins one (all of them if none does), then {..., that
-// segment} over the positions from the last such on.  count >= 1, n >= 1.
+// segment} over the positions from the last such on.  count >= 1, n >= 1.  val_shift, val_mask:
+// the value's bit_field.
 template <bool LENS, bool VALS>
 __global__ void __launch_bounds__(THREADS, 3) // (three waves a SIMD: the gathers want them)
 reduce_tiles(places f, const uint64_t *__restrict__ ret, uint32_t val_shift, uint64_t val_mask,
@@ -257,9 +225,7 @@ reduce_tiles(places f, const uint64_t *__restrict__ ret, uint32_t val_shift, uin
 	const uint64_t R = segments_of(cap, nseg);
 	uint64_t *row = rows + (size_t)blockIdx.x * 2 * ROW;
 	const uint64_t first = (uint64_t)blockIdx.x * TILE;
-	// the list ends where the last segment does
-	uint64_t end = R != 0 ? S[R] : 0;
-	end = end < n ? end : n;
+	const uint64_t end = seg_end(S, R, n); // the list ends where the last segment does
 	if (first >= end) { // (the same for every thread)
 		if (tid == 0) {
 			store_row<LENS, VALS>(row, nothing());
@@ -290,9 +256,8 @@ reduce_tiles(places f, const uint64_t *__restrict__ ret, uint32_t val_shift, uin
 	const uint64_t lo = range[0] != 0 ? range[0] - 1 : 0;
 	const uint64_t hi = range[1] < R ? range[1] : R;
 	for (uint64_t g = lo + tid; g < hi; g += THREADS) {
-		uint64_t a = S[g], b = S[g + 1];
-		a = a < n ? a : n;
-		b = b < n ? b : n;
+		uint64_t a, b;
+		seg_bounds(S, g, n, a, b);
 		if (a < b && a >= first && a - first < TILE)
 			sseg[slot((uint32_t)(a - first))] = (uint32_t)g;
 	}
@@ -305,7 +270,7 @@ reduce_tiles(places f, const uint64_t *__restrict__ ret, uint32_t val_shift, uin
 		idx[k] = sidx[slot(tid * PER_THREAD + k)];
 		has[k] = first + tid * PER_THREAD + k < end && idx[k] < f.count;
 	}
-	fields_of<LENS, VALS>(f, ret, val_shift, val_mask, idx, has, len, val);
+	fields_of<LENS, VALS>(f, ret, {val_shift, val_mask}, idx, has, len, val);
 	__syncthreads();
 	uint32_t seg[PER_THREAD];
 #pragma unroll
@@ -331,7 +296,7 @@ reduce_tiles(places f, const uint64_t *__restrict__ ret, uint32_t val_shift, uin
 		}
 		add<LENS, VALS>(mine, entry(k));
 	}
-	part cur = carry_in<LENS, VALS, WAVES>(mine, wtot);
+	part cur = carry_in<WAVES, join<LENS, VALS>, lane_up<LENS, VALS>>(mine, nothing(), wtot);
 	// The marked positions before this thread's, and the tile's.  All but the last close a
 	// segment inside the tile; many of them go out through LDS (every thread decides alike).
 	uint32_t marked = 0;
@@ -399,23 +364,22 @@ tile_tail(const uint64_t *__restrict__ rows, uint32_t t)
 	return p;
 }
 
-// One workgroup: thread s walks tiles [s * seglen, (s + 1) * seglen) twice, first for what the
-// run hands on, then, with what the threads before it hand in, to close the segments that cross
-// tile edges: each is written where the next segment begins, the last one by the last tile.
+// One workgroup: a thread walks its run of tiles (run_of) twice, first for what the run hands
+// on, then, with what the threads before it hand in, to close the segments that cross tile
+// edges: each is written where the next segment begins, the last one by the last tile.
 template <bool LENS, bool VALS>
 __global__ void __launch_bounds__(CARRY_THREADS)
 reduce_carry(const uint64_t *__restrict__ rows, uint32_t ntiles, uint64_t cap,
 	     const uint64_t *__restrict__ nseg, sums out)
 {
 	__shared__ part wtot[CARRY_THREADS / 64];
-	const uint32_t tid = threadIdx.x;
 	const uint64_t R = segments_of(cap, nseg);
-	const uint32_t seglen = (ntiles + CARRY_THREADS - 1) / CARRY_THREADS;
-	const uint32_t t0 = min(tid * seglen, ntiles), t1 = min(t0 + seglen, ntiles);
+	const auto [t0, t1] = run_of(ntiles);
 	part mine = nothing();
 	for (uint32_t t = t0; t < t1; t++)
 		mine = join<LENS, VALS>(mine, tile_tail<LENS, VALS>(rows, t));
-	part cur = carry_in<LENS, VALS, CARRY_THREADS / 64>(mine, wtot);
+	part cur =
+	    carry_in<CARRY_THREADS / 64, join<LENS, VALS>, lane_up<LENS, VALS>>(mine, nothing(), wtot);
 	for (uint32_t t = t0; t < t1; t++) {
 		const uint64_t *row = rows + (size_t)t * 2 * ROW;
 		const part head = load_row<LENS, VALS>(row);
@@ -438,9 +402,8 @@ reduce_empty(const uint64_t *__restrict__ S, uint64_t n, uint64_t cap,
 	const uint64_t g = (uint64_t)blockIdx.x * THREADS + threadIdx.x;
 	if (g >= segments_of(cap, nseg))
 		return;
-	uint64_t a = S[g], b = S[g + 1];
-	a = a < n ? a : n;
-	b = b < n ? b : n;
+	uint64_t a, b;
+	seg_bounds(S, g, n, a, b);
 	if (a < b)
 		return;
 	if (out.bytes != nullptr)
@@ -453,19 +416,6 @@ reduce_empty(const uint64_t *__restrict__ S, uint64_t n, uint64_t cap,
 		out.max[g] = 0;
 	if (out.bits != nullptr)
 		out.bits[g] = 0;
-}
-
-template <bool LENS, bool VALS>
-void
-launch_typed(const places &f, const uint64_t *ret, uint32_t val_shift, uint64_t val_mask,
-	     const uint32_t *index, uint64_t n, const uint64_t *S, uint64_t cap, const uint64_t *nseg,
-	     const sums &out, uint64_t *rows, hipStream_t stream)
-{
-	const uint32_t ntiles = (uint32_t)((n + TILE - 1) / TILE);
-	hipLaunchKernelGGL((reduce_tiles<LENS, VALS>), dim3(ntiles), dim3(THREADS), 0, stream, f, ret,
-			   val_shift, val_mask, index, n, S, cap, nseg, out, rows);
-	hipLaunchKernelGGL((reduce_carry<LENS, VALS>), dim3(1), dim3(CARRY_THREADS), 0, stream, rows,
-			   ntiles, cap, nseg, out);
 }
 
 } // namespace
@@ -487,16 +437,17 @@ launch_reduce(const struct ebpf_pkt_batch *batch, const uint64_t *ret, uint64_t 
 			  out.bits != nullptr;
 	if (n != 0) {
 		const places f = lens ? places_of(*batch) : places{nullptr, count, 0, 0};
-		const uint64_t mask = val_bits >= 64 ? ~0ull : (1ull << val_bits) - 1;
-		if (lens && vals)
-			launch_typed<true, true>(f, ret, val_shift, mask, index, n, seg_starts, seg_cap, nseg,
-						 out, scratch, stream);
-		else if (lens)
-			launch_typed<true, false>(f, ret, val_shift, mask, index, n, seg_starts, seg_cap, nseg,
-						  out, scratch, stream);
-		else
-			launch_typed<false, true>(f, ret, val_shift, mask, index, n, seg_starts, seg_cap, nseg,
-						  out, scratch, stream);
+		const bit_field vf = field_of(val_shift, val_bits);
+		const uint32_t ntiles = (uint32_t)((n + TILE - 1) / TILE);
+		with_flags([&](auto L, auto V) {
+			if constexpr (L || V) { // (one output is wanted: no kernels for neither)
+				hipLaunchKernelGGL((reduce_tiles<L, V>), dim3(ntiles), dim3(THREADS), 0, stream, f,
+						   ret, vf.shift, vf.mask, index, n, seg_starts, seg_cap, nseg, out,
+						   scratch);
+				hipLaunchKernelGGL((reduce_carry<L, V>), dim3(1), dim3(CARRY_THREADS), 0, stream,
+						   scratch, ntiles, seg_cap, nseg, out);
+			}
+		}, lens, vals);
 	}
 	const uint32_t blocks = (uint32_t)((seg_cap + THREADS - 1) / THREADS);
 	hipLaunchKernelGGL(reduce_empty, dim3(blocks), dim3(THREADS), 0, stream, seg_starts, n, seg_cap,

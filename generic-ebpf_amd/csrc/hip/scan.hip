@@ -30,20 +30,14 @@
 #include <hip/hip_runtime.h>
 
 #include "ebpf_gpu.h"
-#include "hip/batch_places.h"
+#include "hip/seg_tile.h"
 #include "host/scan.h"
-#include "host/steer.h"
 
 namespace {
 
-constexpr uint32_t TILE = STEER_TILE;
-constexpr uint32_t PER_THREAD = TILE / THREADS;
-constexpr uint32_t NOHEAD = ~0u;         // no segment begins here (a segment's number is below it)
-constexpr uint32_t NOPOS = ~0u;          // no segment has begun in the tile yet
-constexpr uint32_t CARRY_THREADS = 1024; // scan_carry's one workgroup
+constexpr uint32_t NOPOS = ~0u; // no segment has begun in the tile yet
 constexpr uint32_t ROW = SCAN_ROW_WORDS;
 constexpr uint32_t SLOTS = TILE + TILE / 16;
-static_assert(PER_THREAD == 16, "a thread's positions are one padded LDS row");
 
 typedef struct ebpf_batch_scans scans;
 
@@ -53,6 +47,7 @@ struct part {
 	uint64_t bytes, sum;
 	uint32_t pos;
 };
+constexpr part NOTHING = {0, 0, NOPOS};
 
 // The segmented scan's operator: run a, then run b.  A segment that begins in b closes a.
 template <bool LENS, bool VALS>
@@ -80,33 +75,6 @@ lane_up(const part &p, uint32_t d)
 	if (VALS)
 		r.sum = __shfl_up((unsigned long long)p.sum, d);
 	return r;
-}
-
-// The join of the runs of the threads before this one, in thread order.  wtot: a part per wave,
-// in LDS.
-template <bool LENS, bool VALS, uint32_t NW>
-__device__ __forceinline__ part
-carry_in(const part &mine, part *wtot)
-{
-	const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-	part inc = mine; // inclusive scan over the wave
-#pragma unroll
-	for (uint32_t d = 1; d < 64; d <<= 1) {
-		const part up = lane_up<LENS, VALS>(inc, d);
-		if (lane >= d)
-			inc = join<LENS, VALS>(up, inc);
-	}
-	if (lane == 63)
-		wtot[w] = inc;
-	__syncthreads();
-	part before = {0, 0, NOPOS};
-	for (uint32_t q = 0; q < NW; q++) {
-		const part s = wtot[q];
-		if (q < w)
-			before = join<LENS, VALS>(before, s);
-	}
-	const part prev = lane_up<LENS, VALS>(inc, 1);
-	return lane == 0 ? before : join<LENS, VALS>(before, prev);
 }
 
 // slot(k * THREADS + threadIdx.x), the thread's k-th position in tile order: a constant apart.
@@ -216,7 +184,7 @@ zero_tile(const scans &out, uint64_t first, uint64_t n)
 
 // LENS: bytes_before or over is wanted; VALS: sum_before is.  With neither, rank alone is
 // computed, rows is not used, and the other outputs that are given are set to 0 (count == 0).
-// n >= 1; count >= 1 where LENS or VALS.
+// n >= 1; count >= 1 where LENS or VALS.  val_shift, val_mask: the value's bit_field.
 template <bool LENS, bool VALS>
 __global__ void __launch_bounds__(THREADS, 3) // (three waves a SIMD: the gathers want them)
 scan_tiles(places f, const uint64_t *__restrict__ ret, uint32_t val_shift, uint64_t val_mask,
@@ -235,9 +203,7 @@ scan_tiles(places f, const uint64_t *__restrict__ ret, uint32_t val_shift, uint6
 	const uint64_t R = segments_of(cap, nseg);
 	uint64_t *row = rows + (size_t)blockIdx.x * ROW;
 	const uint64_t first = (uint64_t)blockIdx.x * TILE;
-	// the segments end where the last one does
-	uint64_t end = R != 0 ? S[R] : 0;
-	end = end < n ? end : n;
+	const uint64_t end = seg_end(S, R, n); // the segments end where the last one does
 	if (first >= end) { // (the same for every thread) no segment covers any of the tile
 #pragma unroll
 		for (uint32_t k = 0; k < PER_THREAD; k++) {
@@ -279,9 +245,8 @@ scan_tiles(places f, const uint64_t *__restrict__ ret, uint32_t val_shift, uint6
 	const uint64_t lo = held ? range[0] - 1 : 0;
 	const uint64_t hi = range[1] < R ? range[1] : R;
 	for (uint64_t g = lo + tid; g < hi; g += THREADS) {
-		uint64_t a = S[g], b = S[g + 1];
-		a = a < n ? a : n;
-		b = b < n ? b : n;
+		uint64_t a, b;
+		seg_bounds(S, g, n, a, b);
 		if (a < b && a >= first && a - first < TILE)
 			sseg[slot((uint32_t)(a - first))] = (uint32_t)g;
 	}
@@ -298,7 +263,7 @@ scan_tiles(places f, const uint64_t *__restrict__ ret, uint32_t val_shift, uint6
 			idx[k] = sidx[slot(tid * PER_THREAD + k)];
 			has[k] = k < mine_live && idx[k] < f.count;
 		}
-		fields_of<LENS, VALS>(f, ret, val_shift, val_mask, idx, has, len, val);
+		fields_of<LENS, VALS>(f, ret, {val_shift, val_mask}, idx, has, len, val);
 #pragma unroll
 		for (uint32_t k = 0; k < PER_THREAD; k++)
 			val[k] = has[k] ? val[k] : 0; // (an entry past the batch has no value)
@@ -312,9 +277,8 @@ scan_tiles(places f, const uint64_t *__restrict__ ret, uint32_t val_shift, uint6
 	// (sidx and sseg are free: every thread has its entries and marks in registers)
 	if (LENS && out.over != nullptr) {
 		for (uint64_t g = lo + tid; g < hi; g += THREADS) {
-			uint64_t a = S[g], b = S[g + 1];
-			a = a < n ? a : n;
-			b = b < n ? b : n;
+			uint64_t a, b;
+			seg_bounds(S, g, n, a, b);
 			if (a < b && a >= first && a - first < TILE)
 				stage[slot((uint32_t)(a - first))] = budgets[g];
 		}
@@ -330,7 +294,7 @@ scan_tiles(places f, const uint64_t *__restrict__ ret, uint32_t val_shift, uint6
 	}
 	// What leaves the thread on its right, its last run, and what lies before its first marked
 	// position (fpos; all of its positions if it has none).
-	part mine = {0, 0, NOPOS}, head = {0, 0, NOPOS};
+	part mine = NOTHING, head = NOTHING;
 	uint32_t fpos = NOPOS;
 #pragma unroll
 	for (uint32_t k = 0; k < PER_THREAD; k++) {
@@ -350,7 +314,8 @@ scan_tiles(places f, const uint64_t *__restrict__ ret, uint32_t val_shift, uint6
 		fpos += q0;
 		mine.pos += q0;
 	}
-	const part in = carry_in<LENS, VALS, WAVES>(mine, wtot); // (and the budgets are in LDS)
+	// (and the budgets are in LDS)
+	const part in = carry_in<WAVES, join<LENS, VALS>, lane_up<LENS, VALS>>(mine, NOTHING, wtot);
 	// The positions that a segment covers: those before the end, from the first marked one on,
 	// or all of them if a segment is open at the thread's first.
 	uint32_t covered = marks;
@@ -421,20 +386,18 @@ tile_tail(const uint64_t *__restrict__ rows, uint32_t t)
 	return {begins ? row[3] : row[0], begins ? row[4] : row[1], begins ? 0u : NOPOS};
 }
 
-// One workgroup: thread s walks tiles [s * seglen, (s + 1) * seglen) twice, first for what the
-// run hands on, then, with what the threads before it hand in, to leave in every tile's row what
-// the segment that is open at the tile's first position accumulated before it.
+// One workgroup: a thread walks its run of tiles (run_of) twice, first for what the run hands
+// on, then, with what the threads before it hand in, to leave in every tile's row what the
+// segment that is open at the tile's first position accumulated before it.
 __global__ void __launch_bounds__(CARRY_THREADS)
 scan_carry(uint64_t *__restrict__ rows, uint32_t ntiles)
 {
 	__shared__ part wtot[CARRY_THREADS / 64];
-	const uint32_t tid = threadIdx.x;
-	const uint32_t seglen = (ntiles + CARRY_THREADS - 1) / CARRY_THREADS;
-	const uint32_t t0 = min(tid * seglen, ntiles), t1 = min(t0 + seglen, ntiles);
-	part mine = {0, 0, NOPOS};
+	const auto [t0, t1] = run_of(ntiles);
+	part mine = NOTHING;
 	for (uint32_t t = t0; t < t1; t++)
 		mine = join<true, true>(mine, tile_tail(rows, t));
-	part cur = carry_in<true, true, CARRY_THREADS / 64>(mine, wtot);
+	part cur = carry_in<CARRY_THREADS / 64, join<true, true>, lane_up<true, true>>(mine, NOTHING, wtot);
 	for (uint32_t t = t0; t < t1; t++) {
 		uint64_t *row = rows + (size_t)t * ROW;
 		row[7] = cur.bytes;
@@ -506,26 +469,6 @@ scan_fix(const uint64_t *__restrict__ rows, places f, const uint32_t *__restrict
 	}
 }
 
-template <bool LENS, bool VALS>
-void
-launch_typed(const places &f, const uint64_t *ret, uint32_t val_shift, uint64_t val_mask,
-	     const uint32_t *index, uint64_t n, const uint64_t *S, uint64_t cap, const uint64_t *nseg,
-	     const uint64_t *budgets, const scans &out, uint64_t *rows, hipStream_t stream)
-{
-	const uint32_t ntiles = (uint32_t)((n + TILE - 1) / TILE);
-	hipLaunchKernelGGL((scan_tiles<LENS, VALS>), dim3(ntiles), dim3(THREADS), 0, stream, f, ret,
-			   val_shift, val_mask, index, n, S, cap, nseg, budgets, out, rows);
-	if ((!LENS && !VALS) || ntiles < 2) // (the first tile's leading positions have nothing before them)
-		return;
-	hipLaunchKernelGGL(scan_carry, dim3(1), dim3(CARRY_THREADS), 0, stream, rows, ntiles);
-	if (out.bytes_before == nullptr && out.over != nullptr)
-		hipLaunchKernelGGL(scan_fix<true>, dim3(ntiles - 1), dim3(THREADS), 0, stream, rows, f,
-				   index, n, out);
-	else
-		hipLaunchKernelGGL(scan_fix<false>, dim3(ntiles - 1), dim3(THREADS), 0, stream, rows, f,
-				   index, n, out);
-}
-
 } // namespace
 
 size_t
@@ -543,18 +486,19 @@ launch_scan(const struct ebpf_pkt_batch *batch, const uint64_t *ret, uint64_t co
 	const bool lens = count != 0 && (out.bytes_before != nullptr || out.over != nullptr);
 	const bool vals = count != 0 && out.sum_before != nullptr;
 	const places f = lens ? places_of(*batch) : places{nullptr, count, 0, 0};
-	const uint64_t mask = val_bits >= 64 ? ~0ull : (1ull << val_bits) - 1;
-	if (lens && vals)
-		launch_typed<true, true>(f, ret, val_shift, mask, index, n, seg_starts, seg_cap, nseg,
-					 budgets, out, scratch, stream);
-	else if (lens)
-		launch_typed<true, false>(f, ret, val_shift, mask, index, n, seg_starts, seg_cap, nseg,
-					  budgets, out, scratch, stream);
-	else if (vals)
-		launch_typed<false, true>(f, ret, val_shift, mask, index, n, seg_starts, seg_cap, nseg,
-					  budgets, out, scratch, stream);
-	else
-		launch_typed<false, false>(f, ret, val_shift, mask, index, n, seg_starts, seg_cap, nseg,
-					   budgets, out, scratch, stream);
+	const bit_field vf = field_of(val_shift, val_bits);
+	const uint32_t ntiles = (uint32_t)((n + TILE - 1) / TILE);
+	with_flags([&](auto L, auto V) {
+		hipLaunchKernelGGL((scan_tiles<L, V>), dim3(ntiles), dim3(THREADS), 0, stream, f, ret, vf.shift,
+				   vf.mask, index, n, seg_starts, seg_cap, nseg, budgets, out, scratch);
+	}, lens, vals);
+	if ((!lens && !vals) || ntiles < 2) // (the first tile's leading positions have nothing before them)
+		return hipGetLastError();
+	hipLaunchKernelGGL(scan_carry, dim3(1), dim3(CARRY_THREADS), 0, stream, scratch, ntiles);
+	// (over without bytes_before: the lengths are fetched again)
+	with_flags([&](auto G) {
+		hipLaunchKernelGGL(scan_fix<G>, dim3(ntiles - 1), dim3(THREADS), 0, stream, scratch, f, index, n,
+				   out);
+	}, out.bytes_before == nullptr && out.over != nullptr);
 	return hipGetLastError();
 }

@@ -2,7 +2,7 @@
 // (ebpf_batch_filter, the statement of the semantics) and on the device (ebpf_batch_filter_dev,
 // filter.hip).
 #include "filter.h"
-#include "runtime.h"
+#include "list_args.h"
 
 namespace {
 
@@ -13,9 +13,9 @@ filter_args(const struct ebpf_batch_test *test, uint64_t count, const uint32_t *
 {
 	if (test == nullptr || out == nullptr || info == nullptr)
 		return fail(EINVAL, "test, out or info is NULL");
-	if (test->ret != nullptr &&
-	    (test->val_bits < 1 || test->val_bits > 64 || test->val_shift > 64 - test->val_bits))
-		return fail(EINVAL, "val_bits outside [1, 64], or val_shift + val_bits above 64");
+	if (test->ret != nullptr)
+		if (int err = check_field(test->val_shift, test->val_bits))
+			return err;
 	if (n != 0 && index == nullptr)
 		return fail(EINVAL, "index is NULL with n > 0");
 	if (seg_starts == nullptr) {
@@ -24,9 +24,7 @@ filter_args(const struct ebpf_batch_test *test, uint64_t count, const uint32_t *
 		if (out->kept_starts != nullptr || out->dropped_starts != nullptr)
 			return fail(EINVAL, "a table is wanted of an unsegmented list");
 	}
-	if (n > 0xffffffffull || count > 0xffffffffull || seg_cap > 0xffffffffull)
-		return fail(E2BIG, "n, count or seg_cap above 2^32 - 1");
-	return 0;
+	return check_sizes(n, count, seg_cap);
 }
 
 } // namespace
@@ -40,21 +38,16 @@ ebpf_batch_filter(const struct ebpf_batch_test *test, uint64_t count, const uint
 	int err = filter_args(test, count, index, n, seg_starts, seg_cap, nseg, out, info);
 	if (err)
 		return err;
-	const uint64_t R = nseg == nullptr ? seg_cap
-			   : *nseg <= seg_cap ? *nseg
-					      : (seg_cap != 0 ? seg_cap - 1 : 0);
-	for (uint64_t g = 0; g < R; g++)
-		if (seg_starts[g] > seg_starts[g + 1])
-			return fail(EINVAL, "seg_starts decreases");
-	if (seg_cap != 0 && seg_starts[R] > n)
-		return fail(EINVAL, "seg_starts ends past n");
+	const uint64_t R = seg_count(nseg, seg_cap);
+	if ((err = check_segments(seg_starts, R, seg_cap, n)))
+		return err;
 	// the positions that take part
 	uint64_t first = 0, end = n;
 	if (seg_starts != nullptr) {
 		first = R != 0 ? seg_starts[0] : 0;
 		end = R != 0 ? seg_starts[R] : 0;
 	}
-	const uint64_t mask = test->val_bits >= 64 ? ~0ull : (1ull << test->val_bits) - 1;
+	const bit_field vf = field_of(test->val_shift, test->val_bits);
 	uint64_t K = 0, D = 0, g = 0;
 	for (uint64_t j = first; j < end; j++) {
 		// the segments that begin here hold what was counted before this position
@@ -72,7 +65,7 @@ ebpf_batch_filter(const struct ebpf_batch_test *test, uint64_t count, const uint
 			pass = pass && test->rank[j] < test->rank_below;
 		if (test->ret != nullptr) {
 			if (i < count) {
-				const uint64_t v = (test->ret[i] >> test->val_shift) & mask;
+				const uint64_t v = vf.of(test->ret[i]);
 				pass = pass && test->val_lo <= v && v <= test->val_hi;
 			} else {
 				pass = false;
@@ -114,16 +107,9 @@ ebpf_batch_filter_dev(int device, const struct ebpf_batch_test *test, uint64_t c
 			      info_dev);
 	if (err || (err = check_device(device)))
 		return err;
-	device_guard dg;
-	hipStream_t st = static_cast<hipStream_t>(stream);
-	hipError_t e = hipSetDevice(device);
-	if (e != hipSuccess)
-		return hip_fail(e, "hipSetDevice");
-	uint32_t *scratch = nullptr;
-	// (the steering rows' buffer: calls on a stream run in order, so they share it)
-	if ((err = steer_acquire(device, st, filter_scratch_bytes(n), &scratch)))
-		return fail(err, "filter scratch");
-	e = launch_filter(*test, count, index_dev, n, seg_starts_dev, seg_cap, nseg_dev, *out, info_dev,
-			  scratch, st);
-	return e == hipSuccess ? 0 : hip_fail(e, "filter kernels");
+	return on_device(device, stream, filter_scratch_bytes(n), "filter kernels",
+			 [&](hipStream_t st, uint32_t *scratch) {
+		return launch_filter(*test, count, index_dev, n, seg_starts_dev, seg_cap, nseg_dev, *out,
+				     info_dev, scratch, st);
+	});
 }

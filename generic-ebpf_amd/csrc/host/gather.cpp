@@ -75,22 +75,15 @@ ebpf_batch_gather_dev(int device, const struct ebpf_pkt_batch *batch, const uint
 		return err;
 	if (n == 0 && out_stride != 0)
 		return 0;
-	device_guard dg;
-	hipStream_t st = static_cast<hipStream_t>(stream);
-	hipError_t e = hipSetDevice(device);
-	if (e != hipSuccess)
-		return hip_fail(e, "hipSetDevice");
-	if (n == 0 || batch->count == 0) { // every length is 0: zero slots, or zero offsets
-		e = out_stride != 0 ? hipMemsetAsync(out_dev, 0, n * out_stride, st)
-				    : hipMemsetAsync(out_offsets_dev, 0, (n + 1) * sizeof(uint64_t), st);
-		return e == hipSuccess ? 0 : hip_fail(e, "hipMemsetAsync(gather)");
-	}
-	uint32_t *scratch = nullptr;
-	const size_t need = gather_scratch_bytes(n, out_stride);
-	// (the steering rows' buffer: calls on a stream run in order, so the two share it)
-	if (need != 0 && (err = steer_acquire(device, st, need, &scratch)))
-		return fail(err, "gather scratch");
-	e = launch_gather(*batch, index_dev, n, out_stride, out_dev, out_bytes, out_offsets_dev,
-			  reinterpret_cast<uint64_t *>(scratch), st);
-	return e == hipSuccess ? 0 : hip_fail(e, "gather kernels");
+	const bool empty = n == 0 || batch->count == 0; // every length is 0: zero slots, or zero offsets
+	return on_device(device, stream, empty ? 0 : gather_scratch_bytes(n, out_stride),
+			 empty ? "hipMemsetAsync(gather)" : "gather kernels",
+			 [&](hipStream_t st, uint32_t *scratch) {
+		if (empty)
+			return out_stride != 0
+				   ? hipMemsetAsync(out_dev, 0, n * out_stride, st)
+				   : hipMemsetAsync(out_offsets_dev, 0, (n + 1) * sizeof(uint64_t), st);
+		return launch_gather(*batch, index_dev, n, out_stride, out_dev, out_bytes, out_offsets_dev,
+				     reinterpret_cast<uint64_t *>(scratch), st);
+	});
 }

@@ -76,6 +76,14 @@ device_count()
 	return n;
 }
 
+int
+check_device(int device)
+{
+	if (device < 0 || device >= device_count())
+		return fail(ENODEV, "no such GPU device");
+	return 0;
+}
+
 static int
 ensure_translated(struct ebpf_prog *ep)
 {

@@ -4,8 +4,8 @@
 #include <numeric>
 #include <vector>
 
-#include "runtime.h"
 #include "group.h"
+#include "list_args.h"
 #include "steer.h"
 
 namespace {
@@ -14,8 +14,8 @@ int
 group_args(const uint64_t *ret, uint64_t count, uint32_t key_shift, uint32_t key_bits,
 	   const uint32_t *index, uint64_t group_cap, const uint64_t *group_starts, const uint64_t *info)
 {
-	if (key_bits < 1 || key_bits > 64 || key_shift > 64 - key_bits)
-		return fail(EINVAL, "key_bits outside [1, 64], or key_shift + key_bits above 64");
+	if (int err = check_field(key_shift, key_bits, "key"))
+		return err;
 	if (info == nullptr || (count != 0 && (ret == nullptr || index == nullptr)))
 		return fail(EINVAL, "ret, index or info is NULL");
 	if (group_cap != 0 && group_starts == nullptr)
@@ -45,7 +45,7 @@ group_tmp_bytes(uint64_t count, uint32_t key_bits)
 EBPF_EXPORT size_t
 ebpf_batch_group_tmp_bytes(uint64_t count, uint32_t key_bits)
 {
-	if (key_bits < 1 || key_bits > 64 || count > 0xffffffffull)
+	if (!field_ok(0, key_bits) || count > 0xffffffffull)
 		return 0;
 	return group_tmp_bytes(count, key_bits);
 }
@@ -59,8 +59,8 @@ ebpf_batch_group(const uint64_t *ret, const uint8_t *faults, uint64_t count, uin
 	int err = group_args(ret, count, key_shift, key_bits, index, group_cap, group_starts, info);
 	if (err)
 		return err;
-	const uint64_t mask = key_bits == 64 ? ~0ull : (1ull << key_bits) - 1;
-	auto key = [&](uint32_t i) { return (ret[i] >> key_shift) & mask; };
+	const bit_field kf = field_of(key_shift, key_bits);
+	auto key = [&](uint32_t i) { return kf.of(ret[i]); };
 	auto faulted = [&](uint32_t i) { return faults != nullptr && faults[i] != 0; };
 	std::vector<uint32_t> order((size_t)count);
 	std::iota(order.begin(), order.end(), 0u);
@@ -110,21 +110,16 @@ ebpf_batch_group_dev(int device, const uint64_t *ret_dev, const uint8_t *faults_
 		return fail(EINVAL, "tmp_dev is NULL");
 	if ((err = check_device(device)))
 		return err;
-	device_guard dg;
-	hipStream_t st = static_cast<hipStream_t>(stream);
-	hipError_t e = hipSetDevice(device);
-	if (e != hipSuccess)
-		return hip_fail(e, "hipSetDevice");
-	if (count == 0) {
-		e = hipMemsetAsync(info_dev, 0, 2 * sizeof(uint64_t), st);
-		if (e == hipSuccess && group_starts_dev != nullptr)
-			e = hipMemsetAsync(group_starts_dev, 0, sizeof(uint64_t), st);
-		return e == hipSuccess ? 0 : hip_fail(e, "hipMemsetAsync(info)");
-	}
-	uint32_t *scratch;
-	if ((err = steer_acquire(device, st, group_scratch_words(count) * sizeof(uint32_t), &scratch)))
-		return fail(err, "grouping scratch");
-	e = launch_group(ret_dev, faults_dev, count, key_shift, key_bits, index_dev, group_cap,
-			 group_keys_dev, group_starts_dev, info_dev, tmp_dev, scratch, st);
-	return e == hipSuccess ? 0 : hip_fail(e, "grouping kernels");
+	return on_device(device, stream, count != 0 ? group_scratch_words(count) * sizeof(uint32_t) : 0,
+			 count != 0 ? "grouping kernels" : "hipMemsetAsync(info)",
+			 [&](hipStream_t st, uint32_t *scratch) {
+		if (count == 0) {
+			hipError_t e = hipMemsetAsync(info_dev, 0, 2 * sizeof(uint64_t), st);
+			if (e == hipSuccess && group_starts_dev != nullptr)
+				e = hipMemsetAsync(group_starts_dev, 0, sizeof(uint64_t), st);
+			return e;
+		}
+		return launch_group(ret_dev, faults_dev, count, key_shift, key_bits, index_dev, group_cap,
+				    group_keys_dev, group_starts_dev, info_dev, tmp_dev, scratch, st);
+	});
 }

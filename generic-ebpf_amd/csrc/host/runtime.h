@@ -1,6 +1,9 @@
-// runtime.h — what the files of the GPU backend share: gpu_runtime.cpp (programs, the launch),
-// stream_scratch.cpp, map_mirror.cpp, map_write_log.cpp, batch.cpp, steer.cpp, gather.cpp, and the launchers
-// they call.
+// runtime.h — what the files of the GPU backend share.  The error and device helpers serve all
+// of them; the stream scratch, the map mirrors and the write log serve the program launches
+// (gpu_runtime.cpp, batch.cpp, pcap.cpp, rccl_sum.cpp, asm_runtime.cpp, asm_jit.cpp);
+// steer_acquire, validate_batch, check_device and on_device serve the list operations (steer.cpp,
+// group.cpp, gather.cpp, scatter.cpp, reduce.cpp, scan.cpp, filter.cpp), whose launchers are
+// declared in each operation's own header.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,6 +15,8 @@
 int fail(int err, const std::string &msg);
 int hip_fail(hipError_t e, const char *what);
 int device_count();
+// ENODEV for a device index that names no GPU
+int check_device(int device);
 // the events of ebpf_gpu_time_next_launch, consumed by the call
 void take_time_events(hipEvent_t *start, hipEvent_t *stop);
 
@@ -95,8 +100,26 @@ int launch(struct ebpf_prog *ep, dprog_device *dp, const dp_launch &L0, hipStrea
 	   hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, bool hist_overwrite = false,
 	   upd_plan *plan = nullptr);
 int validate_batch(const struct ebpf_pkt_batch *b, uint32_t allowed_flags = 0);
-// steer.cpp: ENODEV for a device index that names no GPU (steer.cpp, gather.cpp)
-int check_device(int device);
+
+// A list operation's call on a device, once its arguments are checked and there is work: holds
+// the caller's current device, selects `device`, takes scratch_bytes of the stream's steering
+// scratch (none for 0; calls on a stream run in order, so they share the buffer), runs
+// launch(stream, scratch) and maps its error.  what: the launch, for the messages.
+template <typename F>
+int
+on_device(int device, void *stream, size_t scratch_bytes, const char *what, F launch)
+{
+	device_guard dg;
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	hipError_t e = hipSetDevice(device);
+	if (e != hipSuccess)
+		return hip_fail(e, "hipSetDevice");
+	uint32_t *scratch = nullptr;
+	if (int err = scratch_bytes != 0 ? steer_acquire(device, st, scratch_bytes, &scratch) : 0)
+		return fail(err, std::string("scratch of the ") + what);
+	e = launch(st, scratch);
+	return e == hipSuccess ? 0 : hip_fail(e, what);
+}
 
 hipError_t launch_interp_v0(const dp_launch &L, hipStream_t stream); // interp_v0.hip
 // asm_runtime.cpp

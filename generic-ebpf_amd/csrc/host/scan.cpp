@@ -2,7 +2,7 @@
 // totals per segment"): on the host (ebpf_batch_scan, the statement of the semantics) and on the
 // device (ebpf_batch_scan_dev, scan.hip).
 #include "gather.h"
-#include "runtime.h"
+#include "list_args.h"
 #include "scan.h"
 
 namespace {
@@ -30,28 +30,14 @@ scan_args(const struct ebpf_pkt_batch *batch, const uint64_t *ret, uint64_t coun
 	if (out->sum_before != nullptr) {
 		if (ret == nullptr)
 			return fail(EINVAL, "ret is NULL where sum_before is wanted");
-		if (val_bits < 1 || val_bits > 64 || val_shift > 64 - val_bits)
-			return fail(EINVAL, "val_bits outside [1, 64], or val_shift + val_bits above 64");
+		if (int err = check_field(val_shift, val_bits))
+			return err;
 	}
 	if (wants_lengths(*out) && batch == nullptr)
 		return fail(EINVAL, "batch is NULL where bytes_before or over is wanted");
 	if (out->over != nullptr && budgets == nullptr)
 		return fail(EINVAL, "budgets is NULL where over is wanted");
-	if (batch != nullptr) {
-		// (EBPF_BATCH_HIST_OVERWRITE: as ebpf_batch_reduce, no concern of the packets' places)
-		int err = validate_batch(batch, EBPF_BATCH_HIST_OVERWRITE);
-		if (err)
-			return err;
-		if (batch->count != count)
-			return fail(EINVAL, "batch->count differs from count");
-	}
-	if (n != 0 && index == nullptr)
-		return fail(EINVAL, "index is NULL with n > 0");
-	if (seg_cap != 0 && seg_starts == nullptr)
-		return fail(EINVAL, "seg_starts is NULL with seg_cap > 0");
-	if (n > 0xffffffffull || count > 0xffffffffull || seg_cap > 0xffffffffull)
-		return fail(E2BIG, "n, count or seg_cap above 2^32 - 1");
-	return 0;
+	return check_list(batch, count, index, n, seg_starts, seg_cap);
 }
 
 } // namespace
@@ -67,14 +53,9 @@ ebpf_batch_scan(const struct ebpf_pkt_batch *batch, const uint64_t *ret, uint64_
 			    budgets, out);
 	if (err)
 		return err;
-	const uint64_t R = nseg == nullptr ? seg_cap
-			   : *nseg <= seg_cap ? *nseg
-					      : (seg_cap != 0 ? seg_cap - 1 : 0);
-	for (uint64_t g = 0; g < R; g++)
-		if (seg_starts[g] > seg_starts[g + 1])
-			return fail(EINVAL, "seg_starts decreases");
-	if (seg_cap != 0 && seg_starts[R] > n)
-		return fail(EINVAL, "seg_starts ends past n");
+	const uint64_t R = seg_count(nseg, seg_cap);
+	if ((err = check_segments(seg_starts, R, seg_cap, n)))
+		return err;
 	// the positions that no segment covers
 	for (uint64_t j = 0; j < n; j++) {
 		if (R != 0 && j >= seg_starts[0] && j < seg_starts[R])
@@ -88,7 +69,7 @@ ebpf_batch_scan(const struct ebpf_pkt_batch *batch, const uint64_t *ret, uint64_
 		if (out->over != nullptr)
 			out->over[j] = 0;
 	}
-	const uint64_t mask = val_bits >= 64 ? ~0ull : (1ull << val_bits) - 1;
+	const bit_field vf = field_of(val_shift, val_bits);
 	for (uint64_t g = 0; g < R; g++) {
 		uint64_t bytes = 0, sum = 0;
 		for (uint64_t j = seg_starts[g]; j < seg_starts[g + 1]; j++) {
@@ -108,7 +89,7 @@ ebpf_batch_scan(const struct ebpf_pkt_batch *batch, const uint64_t *ret, uint64_
 				out->over[j] = bytes + len > budgets[g];
 			bytes += len;
 			if (out->sum_before != nullptr && i < count)
-				sum += (ret[i] >> val_shift) & mask;
+				sum += vf.of(ret[i]);
 		}
 	}
 	return 0;
@@ -127,17 +108,11 @@ ebpf_batch_scan_dev(int device, const struct ebpf_pkt_batch *batch, const uint64
 		return err;
 	if (n == 0 || wants_nothing(*out))
 		return 0;
-	device_guard dg;
-	hipStream_t st = static_cast<hipStream_t>(stream);
-	hipError_t e = hipSetDevice(device);
-	if (e != hipSuccess)
-		return hip_fail(e, "hipSetDevice");
-	uint32_t *scratch = nullptr;
-	// (the steering rows' buffer: calls on a stream run in order, so they share it)
+	// (rank alone, or a batch of no packets, keeps no rows)
 	const bool rows = count != 0 && (wants_lengths(*out) || out->sum_before != nullptr);
-	if (rows && (err = steer_acquire(device, st, scan_scratch_bytes(n), &scratch)))
-		return fail(err, "scan scratch");
-	e = launch_scan(batch, ret_dev, count, val_shift, val_bits, index_dev, n, seg_starts_dev,
-			seg_cap, nseg_dev, budgets_dev, *out, reinterpret_cast<uint64_t *>(scratch), st);
-	return e == hipSuccess ? 0 : hip_fail(e, "scan kernels");
+	return on_device(device, stream, rows ? scan_scratch_bytes(n) : 0, "scan kernels",
+			 [&](hipStream_t st, uint32_t *scratch) {
+		return launch_scan(batch, ret_dev, count, val_shift, val_bits, index_dev, n, seg_starts_dev,
+				   seg_cap, nseg_dev, budgets_dev, *out, reinterpret_cast<uint64_t *>(scratch), st);
+	});
 }

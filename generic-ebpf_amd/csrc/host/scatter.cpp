@@ -82,13 +82,9 @@ ebpf_batch_scatter_dev(int device, const struct ebpf_pkt_batch *batch, const uin
 		return err;
 	if (n == 0 || batch->count == 0) // (an empty batch: every length is 0)
 		return 0;
-	device_guard dg;
-	hipError_t e = hipSetDevice(device);
-	if (e != hipSuccess)
-		return hip_fail(e, "hipSetDevice");
-	e = launch_scatter(*batch, index_dev, n, in_stride, in_dev, in_bytes, in_offsets_dev,
-			   static_cast<hipStream_t>(stream));
-	return e == hipSuccess ? 0 : hip_fail(e, "scatter kernels");
+	return on_device(device, stream, 0, "scatter kernels", [&](hipStream_t st, uint32_t *) {
+		return launch_scatter(*batch, index_dev, n, in_stride, in_dev, in_bytes, in_offsets_dev, st);
+	});
 }
 
 EBPF_EXPORT int
@@ -118,11 +114,7 @@ ebpf_batch_merge_dev(int device, uint64_t *ret_dev, uint8_t *faults_dev, uint64_
 		return err;
 	if (n == 0 || count == 0)
 		return 0;
-	device_guard dg;
-	hipError_t e = hipSetDevice(device);
-	if (e != hipSuccess)
-		return hip_fail(e, "hipSetDevice");
-	e = launch_merge(ret_dev, faults_dev, count, index_dev, n, ret2_dev, faults2_dev,
-			 static_cast<hipStream_t>(stream));
-	return e == hipSuccess ? 0 : hip_fail(e, "merge kernel");
+	return on_device(device, stream, 0, "merge kernel", [&](hipStream_t st, uint32_t *) {
+		return launch_merge(ret_dev, faults_dev, count, index_dev, n, ret2_dev, faults2_dev, st);
+	});
 }

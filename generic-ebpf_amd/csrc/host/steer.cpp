@@ -26,14 +26,6 @@ class_of(const uint64_t *ret, const uint8_t *faults, uint64_t i)
 
 } // namespace
 
-int
-check_device(int device)
-{
-	if (device < 0 || device >= device_count())
-		return fail(ENODEV, "no such GPU device");
-	return 0;
-}
-
 // A counting sort: the reference for the device kernels.
 EBPF_EXPORT int
 ebpf_batch_steer(const uint64_t *ret, const uint8_t *faults, uint64_t count, uint32_t *index,
@@ -64,20 +56,13 @@ ebpf_batch_steer_dev(int device, const uint64_t *ret_dev, const uint8_t *faults_
 	int err = steer_args(ret_dev, count, index_dev, starts_dev);
 	if (err || (err = check_device(device)))
 		return err;
-	device_guard dg;
-	hipStream_t st = static_cast<hipStream_t>(stream);
-	hipError_t e = hipSetDevice(device);
-	if (e != hipSuccess)
-		return hip_fail(e, "hipSetDevice");
-	if (count == 0) {
-		e = hipMemsetAsync(starts_dev, 0, EBPF_STEER_STARTS * sizeof(uint64_t), st);
-		return e == hipSuccess ? 0 : hip_fail(e, "hipMemsetAsync(starts)");
-	}
-	uint32_t *scratch;
-	if ((err = steer_acquire(device, st, steer_scratch_words(count) * sizeof(uint32_t), &scratch)))
-		return fail(err, "steering scratch");
-	e = launch_steer(ret_dev, faults_dev, count, index_dev, starts_dev, scratch, st);
-	return e == hipSuccess ? 0 : hip_fail(e, "steering kernels");
+	return on_device(device, stream, count != 0 ? steer_scratch_words(count) * sizeof(uint32_t) : 0,
+			 count != 0 ? "steering kernels" : "hipMemsetAsync(starts)",
+			 [&](hipStream_t st, uint32_t *scratch) {
+		if (count == 0)
+			return hipMemsetAsync(starts_dev, 0, EBPF_STEER_STARTS * sizeof(uint64_t), st);
+		return launch_steer(ret_dev, faults_dev, count, index_dev, starts_dev, scratch, st);
+	});
 }
 
 EBPF_EXPORT int
@@ -95,10 +80,7 @@ ebpf_batch_select_dev(int device, const struct ebpf_pkt_batch *batch, const uint
 		return err;
 	if (n == 0)
 		return 0;
-	device_guard dg;
-	hipError_t e = hipSetDevice(device);
-	if (e != hipSuccess)
-		return hip_fail(e, "hipSetDevice");
-	e = launch_select(*batch, index_dev, n, extents_dev, static_cast<hipStream_t>(stream));
-	return e == hipSuccess ? 0 : hip_fail(e, "select kernel");
+	return on_device(device, stream, 0, "select kernel", [&](hipStream_t st, uint32_t *) {
+		return launch_select(*batch, index_dev, n, extents_dev, st);
+	});
 }

@@ -1,5 +1,6 @@
-// steer.h — shared by the host runtime and steer.hip (ebpf_batch_steer_dev, ebpf_batch_select_dev:
-// a batch's packets grouped by verdict class on the device).
+// steer.h — shared by steer.cpp and steer.hip (ebpf_batch_steer_dev, ebpf_batch_select_dev: a
+// batch's packets grouped by verdict class on the device).  STEER_TILE is every list kernel's tile
+// (hip/wave_rank.h: steer, group; hip/seg_tile.h: reduce, scan, filter); group.hip shares the scan.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

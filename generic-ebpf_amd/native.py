@@ -186,6 +186,13 @@ EBPF_NO_PACKET = 0xffffffff  # EBPF_NO_PACKET: a list entry that names no packet
 STEER_TILE = 4096           # csrc/host/steer.h STEER_TILE: packets per workgroup of the kernels
 
 
+def _pkt_batch(data_ptr, offsets_ptr, count, stride, extents=False, hist_overwrite=False):
+    """The ebpf_pkt_batch of a call: where the packets are, and the two flags."""
+    return PktBatch(data_ptr, offsets_ptr, count, stride,
+                    (BATCH_EXTENTS if extents else 0) |
+                    (BATCH_HIST_OVERWRITE if hist_overwrite else 0))
+
+
 class _AsyncJob:
     """An ebpf_prog_run_batch_async job and the buffers it writes (see Prog.run_batch_async)."""
 
@@ -454,8 +461,8 @@ class Prog:
         ret = np.zeros(count, dtype=np.uint64)
         faults = np.zeros(count, dtype=np.uint8) if want_faults else None
         offs = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
-        b = PktBatch(data.ctypes.data, None if offs is None else offs.ctypes.data, count,
-                     stride, BATCH_EXTENTS if extents else 0)
+        b = _pkt_batch(data.ctypes.data, None if offs is None else offs.ctypes.data,
+                       count, stride, extents)
         st = BatchStats()
         _check(lib().ebpf_prog_run_batch(self.ptr, ctypes.byref(b), ret.ctypes.data,
                                          None if faults is None else faults.ctypes.data,
@@ -468,8 +475,8 @@ class Prog:
         references)."""
         assert data.dtype == np.uint8 and data.flags["C_CONTIGUOUS"]
         job = _AsyncJob(data, count, offsets, want_faults)
-        b = PktBatch(data.ctypes.data, None if job.offs is None else job.offs.ctypes.data, count,
-                     stride, 0)
+        b = _pkt_batch(data.ctypes.data, None if job.offs is None else job.offs.ctypes.data,
+                       count, stride)
         h = ctypes.c_void_p()
         _check(lib().ebpf_prog_run_batch_async(self.ptr, ctypes.byref(b), job.ret.ctypes.data,
                                                None if job.faults is None else job.faults.ctypes.data,
@@ -496,8 +503,8 @@ class Prog:
         ret = np.zeros(count, dtype=np.uint64)
         faults = np.zeros(count, dtype=np.uint8) if want_faults else None
         offs = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
-        b = PktBatch(data.ctypes.data, None if offs is None else offs.ctypes.data, count,
-                     stride, BATCH_EXTENTS if extents else 0)
+        b = _pkt_batch(data.ctypes.data, None if offs is None else offs.ctypes.data,
+                       count, stride, extents)
         devs = (ctypes.c_int * len(devices))(*devices)
         st = BatchStats()
         _check(lib().ebpf_prog_run_batch_multi(self.ptr, len(devices), devs, ctypes.byref(b),
@@ -513,7 +520,7 @@ class Prog:
         n = len(devices)
         arr = (PktBatch * n)()
         for d, (dp, cnt, stride, op) in enumerate(shards):
-            arr[d] = PktBatch(dp, op, cnt, stride, BATCH_HIST_OVERWRITE if hist_overwrite else 0)
+            arr[d] = _pkt_batch(dp, op, cnt, stride, hist_overwrite=hist_overwrite)
         P = ctypes.c_void_p * n
         _check(lib().ebpf_prog_run_batch_multi_dev(
             self.ptr, n, (ctypes.c_int * n)(*devices), arr, P(*rets),
@@ -535,9 +542,7 @@ class Prog:
                       extents=False):
         """Device pointers (ints); asynchronous on ``stream`` (hipStream_t as int or None).
         ``hist_overwrite``: the histogram is set to this batch's counts instead of added to."""
-        b = PktBatch(data_ptr, offsets_ptr, count, stride,
-                     (BATCH_HIST_OVERWRITE if hist_overwrite else 0) |
-                     (BATCH_EXTENTS if extents else 0))
+        b = _pkt_batch(data_ptr, offsets_ptr, count, stride, extents, hist_overwrite=hist_overwrite)
         _check(lib().ebpf_prog_run_batch_dev(self.ptr, device, ctypes.byref(b), ret_ptr,
                                              faults_ptr, hist_ptr, stream),
                "ebpf_prog_run_batch_dev")
@@ -548,8 +553,7 @@ class Prog:
         """A prebound ebpf_prog_run_batch_dev for a bench loop: returns ``launch(hist_ptr)``
         whose only per-call work is the C call itself (batch descriptor and argument
         conversion done once here).  Raises EbpfError on a non-zero return."""
-        b = PktBatch(data_ptr, offsets_ptr, count, stride,
-                     BATCH_HIST_OVERWRITE if hist_overwrite else 0)
+        b = _pkt_batch(data_ptr, offsets_ptr, count, stride, hist_overwrite=hist_overwrite)
         f = lib().ebpf_prog_run_batch_dev
         args = (self.ptr, device, ctypes.byref(b), ret_ptr, faults_ptr)
         st = stream
@@ -604,7 +608,7 @@ def select_dev(device, data_ptr, count, stride, index_ptr, n, extents_ptr, offse
     """ebpf_batch_select_dev: the (start, end) pairs of packets index[0..n) of the batch
     (data_ptr, count, stride, offsets_ptr, extents) as run_batch_dev takes it, written to
     ``extents_ptr`` (2n u64); device pointers (ints); asynchronous on ``stream``."""
-    b = PktBatch(data_ptr, offsets_ptr, count, stride, BATCH_EXTENTS if extents else 0)
+    b = _pkt_batch(data_ptr, offsets_ptr, count, stride, extents)
     _check(lib().ebpf_batch_select_dev(device, ctypes.byref(b), index_ptr, n, extents_ptr,
                                        stream), "ebpf_batch_select_dev")
 
@@ -673,8 +677,8 @@ def reduce(index, seg_starts, ret=None, val_shift=0, val_bits=64, count=None, st
     offs = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
     b = None
     if "bytes" in want:   # (data: never read, but a batch with packets names some)
-        b = PktBatch(1 if count else None, None if offs is None else offs.ctypes.data, count,
-                     stride, BATCH_EXTENTS if extents else 0)
+        b = _pkt_batch(1 if count else None, None if offs is None else offs.ctypes.data,
+                       count, stride, extents)
     outs = [np.zeros(cap, dtype=np.uint64) if name in want else None for name in SUMS]
     sums = BatchSums(*[None if o is None or not cap else o.ctypes.data for o in outs])
     ns = None if nseg is None else np.array([nseg], dtype=np.uint64)
@@ -699,8 +703,7 @@ def reduce_dev(device, ret_ptr, count, val_shift, val_bits, index_ptr, n, seg_st
     on ``stream``."""
     b = None
     if bytes_ptr is not None:
-        b = PktBatch(data_ptr or (1 if count else None), offsets_ptr, count, stride,
-                     BATCH_EXTENTS if extents else 0)
+        b = _pkt_batch(data_ptr or (1 if count else None), offsets_ptr, count, stride, extents)
     sums = BatchSums(bytes_ptr, sum_ptr, min_ptr, max_ptr, bits_ptr)
     _check(lib().ebpf_batch_reduce_dev(device, None if b is None else ctypes.byref(b), ret_ptr,
                                        count, val_shift, val_bits, index_ptr, n, seg_starts_ptr,
@@ -738,8 +741,8 @@ def scan(index, seg_starts, ret=None, val_shift=0, val_bits=64, count=None, stri
         assert len(budgets) == cap
     b = None
     if "bytes_before" in want or "over" in want:   # (data: never read)
-        b = PktBatch(1 if count else None, None if offs is None else offs.ctypes.data, count,
-                     stride, BATCH_EXTENTS if extents else 0)
+        b = _pkt_batch(1 if count else None, None if offs is None else offs.ctypes.data,
+                       count, stride, extents)
     outs = [np.zeros(n, dtype=_SCAN_TYPES[name]) if name in want else None for name in SCANS]
     scans = BatchScans(*[None if o is None else o.ctypes.data or 1 for o in outs])
     ns = None if nseg is None else np.array([nseg], dtype=np.uint64)
@@ -766,8 +769,7 @@ def scan_dev(device, ret_ptr, count, val_shift, val_bits, index_ptr, n, seg_star
     (None: a stand-in).  Asynchronous on ``stream``."""
     b = None
     if bytes_before_ptr is not None or over_ptr is not None:
-        b = PktBatch(data_ptr or (1 if count else None), offsets_ptr, count, stride,
-                     BATCH_EXTENTS if extents else 0)
+        b = _pkt_batch(data_ptr or (1 if count else None), offsets_ptr, count, stride, extents)
     scans = BatchScans(rank_ptr, bytes_before_ptr, sum_before_ptr, over_ptr)
     _check(lib().ebpf_batch_scan_dev(device, None if b is None else ctypes.byref(b), ret_ptr,
                                      count, val_shift, val_bits, index_ptr, n, seg_starts_ptr,
@@ -851,8 +853,8 @@ def gather(data, count, index, out_stride=0, stride=0, offsets=None, extents=Fal
     assert data.dtype == np.uint8 and data.flags["C_CONTIGUOUS"]
     index = np.ascontiguousarray(index, dtype=np.uint32)
     offs = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
-    b = PktBatch(data.ctypes.data, None if offs is None else offs.ctypes.data, count, stride,
-                 BATCH_EXTENTS if extents else 0)
+    b = _pkt_batch(data.ctypes.data, None if offs is None else offs.ctypes.data,
+                   count, stride, extents)
     n = len(index)
     f = lib().ebpf_batch_gather
     if out_stride:
@@ -881,7 +883,7 @@ def gather_dev(device, data_ptr, count, stride, index_ptr, n, out_stride, out_pt
     offsets_ptr, extents) as run_batch_dev takes it, copied to ``out_ptr``: slots of
     ``out_stride`` bytes, or (``out_stride`` 0) packed, with their n + 1 offsets written to
     ``out_offsets_ptr``; device pointers (ints); asynchronous on ``stream``."""
-    b = PktBatch(data_ptr, offsets_ptr, count, stride, BATCH_EXTENTS if extents else 0)
+    b = _pkt_batch(data_ptr, offsets_ptr, count, stride, extents)
     _check(lib().ebpf_batch_gather_dev(device, ctypes.byref(b), index_ptr, n, out_stride, out_ptr,
                                        out_bytes, out_offsets_ptr, stream),
            "ebpf_batch_gather_dev")
@@ -898,8 +900,8 @@ def scatter(data, count, index, dense, in_stride=0, stride=0, offsets=None, exte
     index = np.ascontiguousarray(index, dtype=np.uint32)
     offs = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
     in_offs = None if in_offsets is None else np.ascontiguousarray(in_offsets, dtype=np.uint64)
-    b = PktBatch(data.ctypes.data, None if offs is None else offs.ctypes.data, count, stride,
-                 BATCH_EXTENTS if extents else 0)
+    b = _pkt_batch(data.ctypes.data, None if offs is None else offs.ctypes.data,
+                   count, stride, extents)
     _check(lib().ebpf_batch_scatter(ctypes.byref(b), index.ctypes.data, len(index), in_stride,
                                     dense.ctypes.data, len(dense) if in_bytes is None else in_bytes,
                                     None if in_offs is None else in_offs.ctypes.data),
@@ -912,7 +914,7 @@ def scatter_dev(device, data_ptr, count, stride, index_ptr, n, in_stride, in_ptr
     (``in_stride`` 0) packed at the n + 1 offsets of ``in_offsets_ptr``) written back into packets
     index[0..n) of the batch (data_ptr, count, stride, offsets_ptr, extents); device pointers
     (ints); asynchronous on ``stream``."""
-    b = PktBatch(data_ptr, offsets_ptr, count, stride, BATCH_EXTENTS if extents else 0)
+    b = _pkt_batch(data_ptr, offsets_ptr, count, stride, extents)
     _check(lib().ebpf_batch_scatter_dev(device, ctypes.byref(b), index_ptr, n, in_stride, in_ptr,
                                         in_bytes, in_offsets_ptr, stream),
            "ebpf_batch_scatter_dev")
