@@ -93,6 +93,13 @@ class BatchParts(ctypes.Structure):
                 ("dropped", ctypes.c_void_p), ("dropped_starts", ctypes.c_void_p)]
 
 
+class KeyTable(ctypes.Structure):
+    """struct ebpf_key_table: cap keys, strictly ascending, cap values beside them, and the
+    number of keys the table has or would need"""
+    _fields_ = [("keys", ctypes.c_void_p), ("vals", ctypes.c_void_p), ("cap", ctypes.c_uint64),
+                ("n", ctypes.c_void_p)]
+
+
 class BatchStats(ctypes.Structure):
     _fields_ = [("packets", ctypes.c_uint64), ("faulted", ctypes.c_uint64),
                 ("hist", ctypes.c_uint64 * EBPF_HIST_BINS), ("kernel_ms", ctypes.c_double),
@@ -166,6 +173,11 @@ FUNCS = {
                                  _VP]),
     "ebpf_batch_filter": (_I, [_VP, _U64, _VP, _U64, _VP, _U64, _VP, _VP, _VP]),
     "ebpf_batch_filter_dev": (_I, [_I, _VP, _U64, _VP, _U64, _VP, _U64, _VP, _VP, _VP, _VP]),
+    "ebpf_batch_lookup": (_I, [_VP, _VP, _U64, _VP, _U32, _U64, _U64, _VP, _VP]),
+    "ebpf_batch_lookup_dev": (_I, [_I, _VP, _VP, _U64, _VP, _U32, _U64, _U64, _VP, _VP, _VP]),
+    "ebpf_batch_accumulate": (_I, [_VP, _VP, _VP, _U64, _VP, _U32, _U64, _U64, _VP, _VP]),
+    "ebpf_batch_accumulate_dev": (_I, [_I, _VP, _VP, _VP, _U64, _VP, _U32, _U64, _U64, _VP, _VP,
+                                       _VP]),
     "ebpf_batch_gather": (_I, [_VP, _VP, _U64, _U32, _VP, _U64, _VP]),
     "ebpf_batch_gather_dev": (_I, [_I, _VP, _VP, _U64, _U32, _VP, _U64, _VP, _VP]),
     "ebpf_batch_scatter": (_I, [_VP, _VP, _U64, _U32, _VP, _U64, _VP]),
@@ -184,6 +196,9 @@ BATCH_EXTENTS = 0x2         # EBPF_BATCH_EXTENTS: offsets holds (start, end) pai
 STEER_STARTS = EBPF_HIST_BINS + 1  # EBPF_STEER_STARTS: entries of a steering call's starts
 EBPF_NO_PACKET = 0xffffffff  # EBPF_NO_PACKET: a list entry that names no packet
 STEER_TILE = 4096           # csrc/host/steer.h STEER_TILE: packets per workgroup of the kernels
+EBPF_NO_ENTRY = 0xffffffff  # EBPF_NO_ENTRY: the position of a key that a table does not hold
+LOOKUP_VALUE, LOOKUP_REMAINING = 0, 1          # EBPF_LOOKUP_*: the modes of a lookup
+ACC_ADD, ACC_MIN, ACC_MAX, ACC_OR = range(4)   # EBPF_ACC_*: the ops of an accumulate
 
 
 def _pkt_batch(data_ptr, offsets_ptr, count, stride, extents=False, hist_overwrite=False):
@@ -841,6 +856,96 @@ def filter_dev(device, count, index_ptr, n, seg_starts_ptr, seg_cap, info_ptr, n
     _check(lib().ebpf_batch_filter_dev(device, ctypes.byref(test), count, index_ptr, n,
                                        seg_starts_ptr, seg_cap, nseg_ptr, ctypes.byref(parts),
                                        info_ptr, stream), "ebpf_batch_filter_dev")
+
+
+def _key_table(keys, vals, n):
+    """(KeyTable, the arrays it points into) of host arrays; n None: every entry is valid"""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    vals = np.ascontiguousarray(vals, dtype=np.uint64)
+    assert len(keys) == len(vals)
+    cnt = np.array([len(keys) if n is None else n], dtype=np.uint64)
+    cap = len(keys)
+    return KeyTable(keys.ctypes.data if cap else None, vals.ctypes.data if cap else None, cap,
+                    cnt.ctypes.data), (keys, vals, cnt)
+
+
+def lookup(table_keys, table_vals, keys, mode=LOOKUP_VALUE, missing=0, limit=0, n=None,
+           nkeys=None, want=("vals", "pos")):
+    """ebpf_batch_lookup on host arrays: ``keys`` (any order) looked up in the table
+    (``table_keys`` strictly ascending, ``table_vals`` beside them; ``n`` (None: all) is the
+    table's *n).  ``nkeys`` (None: every key) is the number of keys as ebpf_batch_group's info[0]
+    gives it.  Returns (vals u64[key_cap], pos u32[key_cap], code), None where not wanted: per key
+    the table's value or ``missing`` (LOOKUP_VALUE), or what is left of ``limit`` after it
+    (LOOKUP_REMAINING), and its position or EBPF_NO_ENTRY; entries at or past the keys used are 0.
+    code is 0 or errno.EINVAL for a table that is not strictly ascending."""
+    table, hold = _key_table(table_keys, table_vals, n)
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    cap = len(keys)
+    vals = np.zeros(cap, dtype=np.uint64) if "vals" in want else None
+    pos = np.zeros(cap, dtype=np.uint32) if "pos" in want else None
+    nk = None if nkeys is None else np.array([nkeys], dtype=np.uint64)
+    code = lib().ebpf_batch_lookup(ctypes.byref(table), keys.ctypes.data if cap else None, cap,
+                                   None if nk is None else nk.ctypes.data, mode, missing, limit,
+                                   None if vals is None else vals.ctypes.data or 1,
+                                   None if pos is None else pos.ctypes.data or 1)
+    if code not in (0, errno.EINVAL):
+        raise EbpfError(code, "ebpf_batch_lookup")
+    return vals, pos, code
+
+
+def lookup_dev(device, table_keys_ptr, table_vals_ptr, table_cap, table_n_ptr, keys_ptr, key_cap,
+               nkeys_ptr=None, mode=LOOKUP_VALUE, missing=0, limit=0, vals_out_ptr=None,
+               pos_out_ptr=None, stream=None):
+    """ebpf_batch_lookup_dev: device pointers (ints); the table is (keys, vals, cap, n), the
+    outputs that are wanted are given (vals_out key_cap u64, pos_out key_cap u32).  Asynchronous
+    on ``stream``."""
+    table = KeyTable(table_keys_ptr, table_vals_ptr, table_cap, table_n_ptr)
+    _check(lib().ebpf_batch_lookup_dev(device, ctypes.byref(table), keys_ptr, key_cap, nkeys_ptr,
+                                       mode, missing, limit, vals_out_ptr, pos_out_ptr, stream),
+           "ebpf_batch_lookup_dev")
+
+
+def accumulate(table_keys, table_vals, keys, adds, op=ACC_ADD, keep_lo=0, keep_hi=(1 << 64) - 1,
+               out_cap=None, n=None, nkeys=None):
+    """ebpf_batch_accumulate on host arrays: the table (``table_keys`` None: no table; ``n`` as
+    lookup() takes it) merged with the batch's ``keys`` (strictly ascending) and ``adds`` under
+    ``op``, the candidates whose value lies in [keep_lo, keep_hi] kept.  ``out_cap`` (None: room
+    for every candidate) is the new table's cap.  Returns (out_keys u64[out_cap], out_vals
+    u64[out_cap], out_n, info u64[3] = (kept, kept and new, left out), code): entries at or past
+    min(out_n, out_cap) are 0.  code is 0, errno.ENOSPC for out_n > out_cap, or errno.EINVAL for a
+    table or keys that are not strictly ascending."""
+    table, hold = (None, None) if table_keys is None else _key_table(table_keys, table_vals, n)
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    adds = np.ascontiguousarray(adds, dtype=np.uint64)
+    cap = len(keys)
+    assert len(adds) == cap
+    if out_cap is None:
+        out_cap = cap + (0 if table is None else table.cap)
+    out, (okeys, ovals, on) = _key_table(np.zeros(out_cap, dtype=np.uint64),
+                                         np.zeros(out_cap, dtype=np.uint64), 0)
+    info = np.zeros(3, dtype=np.uint64)
+    nk = None if nkeys is None else np.array([nkeys], dtype=np.uint64)
+    code = lib().ebpf_batch_accumulate(None if table is None else ctypes.byref(table),
+                                       keys.ctypes.data if cap else None,
+                                       adds.ctypes.data if cap else None, cap,
+                                       None if nk is None else nk.ctypes.data, op, keep_lo,
+                                       keep_hi, ctypes.byref(out), info.ctypes.data)
+    if code not in (0, errno.EINVAL, errno.ENOSPC):
+        raise EbpfError(code, "ebpf_batch_accumulate")
+    return okeys, ovals, int(on[0]), info, code
+
+
+def accumulate_dev(device, in_table, keys_ptr, adds_ptr, key_cap, out_table, info_ptr,
+                   nkeys_ptr=None, op=ACC_ADD, keep_lo=0, keep_hi=(1 << 64) - 1, stream=None):
+    """ebpf_batch_accumulate_dev: device pointers (ints); ``in_table`` (None: no table) and
+    ``out_table`` are (keys_ptr, vals_ptr, cap, n_ptr); ``info_ptr`` (3 u64) gets the numbers kept,
+    kept and new, and left out.  Asynchronous on ``stream``."""
+    tin = None if in_table is None else KeyTable(*in_table)
+    tout = KeyTable(*out_table)
+    _check(lib().ebpf_batch_accumulate_dev(device, None if tin is None else ctypes.byref(tin),
+                                           keys_ptr, adds_ptr, key_cap, nkeys_ptr, op, keep_lo,
+                                           keep_hi, ctypes.byref(tout), info_ptr, stream),
+           "ebpf_batch_accumulate_dev")
 
 
 def gather(data, count, index, out_stride=0, stride=0, offsets=None, extents=False,

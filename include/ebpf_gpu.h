@@ -675,6 +675,128 @@ int ebpf_batch_filter_dev(int device, const struct ebpf_batch_test *test, uint64
 			  uint64_t seg_cap, const uint64_t *nseg_dev,
 			  const struct ebpf_batch_parts *out, uint64_t *info_dev, void *stream);
 
+/* Carrying totals across batches: a table keyed by the flow key, kept on the device.  A group
+ * number is a position in one batch's group_keys; what outlives the batch — the bytes a flow has
+ * used of a quota, a per-flow counter, a "last seen" stamp — is kept by key, in a sorted table:
+ * keys strictly ascending as unsigned numbers, a value beside each.  A batch's group_keys are
+ * strictly ascending too (a radix sort wrote them), so looking a batch up in the table and folding
+ * a batch's per-group sums into it are merges of two sorted sequences: no hashing, no atomics, no
+ * insertion order.  A byte quota per flow that holds across batches, with tables cur and next:
+ *
+ *   ebpf_batch_group_dev(dev, ret, faults, batch.count, 0, 32, index, cap, keys, starts, info,
+ *                        tmp, tmp_bytes, s);
+ *   ebpf_batch_lookup_dev(dev, &cur, keys, cap, info, EBPF_LOOKUP_REMAINING, 0, quota, budgets,
+ *                         NULL, s);                    (budgets[g] = quota - the bytes used, or 0)
+ *   ebpf_batch_scan_dev(... budgets, &scans, s);  ebpf_batch_filter_dev(... over ... &parts, kd, s);
+ *   sums = {bytes, NULL, NULL, NULL, NULL};
+ *   ebpf_batch_reduce_dev(dev, &batch, NULL, batch.count, 0, 0, kept, batch.count, kept_starts,
+ *                         cap, info, &sums, s);        (bytes[g] = what flow g sent in this batch)
+ *   ebpf_batch_accumulate_dev(dev, &cur, keys, bytes, cap, info, EBPF_ACC_ADD, 0, UINT64_MAX,
+ *                             &next, tinfo, s);        (then swap cur and next)
+ *
+ * The table (struct ebpf_key_table, a host struct): keys and vals have cap entries each, vals[p]
+ *   belongs to keys[p], and *n is the number of keys the table has, or would need (snprintf's
+ *   rule).  N = min(*n, cap) entries are valid and keys[0 .. N) is strictly ascending.  A table that
+ *   an accumulate left short (*n > cap) is its first cap entries, as a short group table is.  An
+ *   empty table is *n == 0.  keys and vals may be NULL iff cap == 0; so may n, which then reads as
+ *   0 and is not written.  cap is at most 0xffffffff: a table position is 32 bits.
+ * The batch's side: keys has key_cap entries, of which R are used, exactly the R of
+ *   ebpf_batch_reduce: key_cap when nkeys is NULL, else *nkeys when *nkeys <= key_cap, else
+ *   key_cap - 1 (0 for key_cap == 0).  So ebpf_batch_group_dev's group_keys, group_cap and info,
+ *   and the members of the ebpf_batch_sums of a reduce that followed it, plug in as they stand,
+ *   after those calls on the same stream: entry g of each belongs to the same flow.
+ *
+ * Lookup, for g < R: p = the position of keys[g] in the table, if it is there;
+ *     pos_out[g]  = p, or EBPF_NO_ENTRY when it is not;
+ *     v           = table->vals[p], or `missing` when it is not;
+ *     vals_out[g] = v for EBPF_LOOKUP_VALUE; for EBPF_LOOKUP_REMAINING limit - v when v < limit,
+ *                   else 0.  With a table of the bytes used per flow and missing = 0 that is the
+ *                   scan's budgets.
+ *   Entries at or past R of either output are not written.  Either output may be NULL: it is not
+ *   wanted and costs nothing; with both NULL the call succeeds and does nothing.  The looked-up
+ *   keys may be in any order and may repeat; only the table must be sorted.
+ *
+ * Accumulate: keys[0 .. R) is strictly ascending and adds[g] belongs to keys[g].  The candidates
+ *   are the union of the N keys of `in` and the batch's R keys, in ascending key order; a
+ *   candidate's value is
+ *     in->vals[p] op adds[g]  for a key in both (keys[g] == in->keys[p]),
+ *     in->vals[p]             for a key in the table alone,
+ *     adds[g]                 for a key in the batch alone,
+ *   with op one of EBPF_ACC_ADD (modulo 2^64), EBPF_ACC_MIN, EBPF_ACC_MAX (unsigned) and
+ *   EBPF_ACC_OR: the reduce's sum, min, max and bits.  A candidate is kept iff keep_lo <= value <=
+ *   keep_hi as unsigned numbers: 0 and UINT64_MAX keep everything; keep_lo > keep_hi is legal and
+ *   keeps nothing.  That is how a table stays bounded: a "last seen" table with EBPF_ACC_MAX and
+ *   keep_lo = now - age forgets idle flows, and a call with R == 0 is a pure prune.  `in` NULL is an
+ *   empty table.  With M the number of kept candidates:
+ *     out->keys[0 .. min(M, out->cap)) and out->vals likewise hold the kept candidates in ascending
+ *       key order; entries at or past min(M, out->cap) are not written;
+ *     *out->n = M even when M > out->cap: the table is complete iff *out->n <= out->cap;
+ *     info (3 entries, always written): info[0] = M; info[1] = the kept candidates whose key was
+ *       not in `in`; info[2] = the candidates left out by the keep range.
+ *   out (its arrays and n) may not overlap `in`, the batch's arrays or info: the caller keeps two
+ *   tables and swaps them.
+ * The output is a function of the inputs alone: it does not depend on what the outputs held on
+ * entry, and two calls on the same input give the same bytes.
+ *
+ * ebpf_batch_lookup, ebpf_batch_accumulate: host buffers (the tables' pointers too), plain loops;
+ *   no GPU needed (the statement of what the device functions compute).  Because they can look,
+ *   they also return EINVAL, with nothing written, when a table's keys[0 .. N) is not strictly
+ *   ascending, and the accumulate when keys[0 .. R) is not.  ebpf_batch_accumulate returns ENOSPC
+ *   when M > out->cap, with everything that fits, *out->n and info written, as ebpf_batch_group
+ *   does.
+ * ebpf_batch_lookup_dev, ebpf_batch_accumulate_dev: every pointer inside the structs and every
+ *   array (keys_dev, adds_dev, nkeys_dev, the outputs, info_dev; the structs themselves are host
+ *   memory) is device memory on `device`; enqueued on `stream` (hipStream_t, NULL = default
+ *   stream), they return without synchronising and never wait for the device.  A short output table
+ *   returns 0: the caller compares info[0] with its cap after the stream.  They cannot look at the
+ *   order of their inputs: for a table or, in the accumulate, keys that are not strictly ascending
+ *   the outputs are unspecified, but every access is clamped: every search ends and stays inside its
+ *   sequence whatever that holds; nothing outside the tables' [0, N), keys[0 .. R), adds[0 .. R),
+ *   *n and *nkeys is read; and nothing outside vals_out[0 .. R), pos_out[0 .. R), out's
+ *   [0, min(M', out->cap)) for the M' written to *out->n, *out->n and info[0 .. 3) is written.
+ *   The cost follows cap and key_cap (the kernels are launched over them), not N and R.
+ *   Temporary storage is the library's, per stream, shared with ebpf_batch_steer_dev,
+ *   ebpf_batch_group_dev, ebpf_batch_reduce_dev, ebpf_batch_scan_dev and ebpf_batch_filter_dev:
+ *   none for the lookup; for the accumulate 648 bytes per 4,096 entries of in->cap and per 4,096
+ *   of key_cap (a bit per entry, a count per 64 entries and two per tile) and 32 bytes a call.
+ *   Every array is 8-byte aligned, pos_out 4-byte aligned, as their types say.
+ * All return 0; EINVAL for a NULL table or out, a NULL info, an unknown mode or op, NULL keys with
+ * key_cap > 0, NULL adds with key_cap > 0, NULL keys, vals or n in a table with cap > 0; then E2BIG
+ * for key_cap or a table's cap above 0xffffffff.  All of these are known on the host, before the
+ * device is looked at.  The device functions then return ENODEV (no GPU, or no such device), ENOMEM
+ * (no scratch) or EIO.  None changes the calling thread's current HIP device. */
+#define EBPF_NO_ENTRY 0xffffffffu   /* pos_out of a key that the table does not hold */
+#define EBPF_LOOKUP_VALUE     0u    /* vals_out[g] = v */
+#define EBPF_LOOKUP_REMAINING 1u    /* vals_out[g] = v < limit ? limit - v : 0 */
+#define EBPF_ACC_ADD 0u             /* modulo 2^64 */
+#define EBPF_ACC_MIN 1u             /* unsigned */
+#define EBPF_ACC_MAX 2u             /* unsigned */
+#define EBPF_ACC_OR  3u
+
+struct ebpf_key_table {   /* a host struct; the pointers are host memory for the host functions,
+                             device memory on `device` for the _dev ones */
+	uint64_t *keys;   /* cap entries; [0, N) strictly ascending as unsigned numbers */
+	uint64_t *vals;   /* cap entries; vals[p] belongs to keys[p] */
+	uint64_t  cap;
+	uint64_t *n;      /* 1 entry: the number of keys the table has, or would need */
+};
+int ebpf_batch_lookup(const struct ebpf_key_table *table, const uint64_t *keys, uint64_t key_cap,
+		      const uint64_t *nkeys, uint32_t mode, uint64_t missing, uint64_t limit,
+		      uint64_t *vals_out, uint32_t *pos_out);
+int ebpf_batch_lookup_dev(int device, const struct ebpf_key_table *table, const uint64_t *keys_dev,
+			  uint64_t key_cap, const uint64_t *nkeys_dev, uint32_t mode,
+			  uint64_t missing, uint64_t limit, uint64_t *vals_out_dev,
+			  uint32_t *pos_out_dev, void *stream);
+int ebpf_batch_accumulate(const struct ebpf_key_table *in, const uint64_t *keys,
+			  const uint64_t *adds, uint64_t key_cap, const uint64_t *nkeys, uint32_t op,
+			  uint64_t keep_lo, uint64_t keep_hi, const struct ebpf_key_table *out,
+			  uint64_t *info);
+int ebpf_batch_accumulate_dev(int device, const struct ebpf_key_table *in,
+			      const uint64_t *keys_dev, const uint64_t *adds_dev, uint64_t key_cap,
+			      const uint64_t *nkeys_dev, uint32_t op, uint64_t keep_lo,
+			      uint64_t keep_hi, const struct ebpf_key_table *out, uint64_t *info_dev,
+			      void *stream);
+
 /* Gathering packets into a dense batch: a list of n packets of `batch` (a class of a steered
  * batch, the whole steering index, any list of the caller's own: duplicates and any order are
  * fine) copied, in list order, into `out`.  A class can then leave the device on its own (a TX
