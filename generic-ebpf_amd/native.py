@@ -100,6 +100,11 @@ class KeyTable(ctypes.Structure):
                 ("n", ctypes.c_void_p)]
 
 
+class BatchTops(ctypes.Structure):
+    """struct ebpf_batch_tops: the outputs of a top call, each NULL or k entries"""
+    _fields_ = [("keys", ctypes.c_void_p), ("vals", ctypes.c_void_p), ("pos", ctypes.c_void_p)]
+
+
 class BatchStats(ctypes.Structure):
     _fields_ = [("packets", ctypes.c_uint64), ("faulted", ctypes.c_uint64),
                 ("hist", ctypes.c_uint64 * EBPF_HIST_BINS), ("kernel_ms", ctypes.c_double),
@@ -178,6 +183,8 @@ FUNCS = {
     "ebpf_batch_accumulate": (_I, [_VP, _VP, _VP, _U64, _VP, _U32, _U64, _U64, _VP, _VP]),
     "ebpf_batch_accumulate_dev": (_I, [_I, _VP, _VP, _VP, _U64, _VP, _U32, _U64, _U64, _VP, _VP,
                                        _VP]),
+    "ebpf_batch_top": (_I, [_VP, _VP, _U64, _VP, _U32, _U32, _U32, _U64, _VP, _VP]),
+    "ebpf_batch_top_dev": (_I, [_I, _VP, _VP, _U64, _VP, _U32, _U32, _U32, _U64, _VP, _VP, _VP]),
     "ebpf_batch_gather": (_I, [_VP, _VP, _U64, _U32, _VP, _U64, _VP]),
     "ebpf_batch_gather_dev": (_I, [_I, _VP, _VP, _U64, _U32, _VP, _U64, _VP, _VP]),
     "ebpf_batch_scatter": (_I, [_VP, _VP, _U64, _U32, _VP, _U64, _VP]),
@@ -199,6 +206,8 @@ STEER_TILE = 4096           # csrc/host/steer.h STEER_TILE: packets per workgrou
 EBPF_NO_ENTRY = 0xffffffff  # EBPF_NO_ENTRY: the position of a key that a table does not hold
 LOOKUP_VALUE, LOOKUP_REMAINING = 0, 1          # EBPF_LOOKUP_*: the modes of a lookup
 ACC_ADD, ACC_MIN, ACC_MAX, ACC_OR = range(4)   # EBPF_ACC_*: the ops of an accumulate
+TOP_MAX = 4096                                 # EBPF_TOP_MAX: the most entries a top call takes
+TOP_LARGEST, TOP_SMALLEST, TOP_SEGMENTS = 0, 1, 2   # EBPF_TOP_*: the flags of a top call
 
 
 def _pkt_batch(data_ptr, offsets_ptr, count, stride, extents=False, hist_overwrite=False):
@@ -946,6 +955,46 @@ def accumulate_dev(device, in_table, keys_ptr, adds_ptr, key_cap, out_table, inf
                                            keys_ptr, adds_ptr, key_cap, nkeys_ptr, op, keep_lo,
                                            keep_hi, ctypes.byref(tout), info_ptr, stream),
            "ebpf_batch_accumulate_dev")
+
+
+def top(keys, vals, k, flags=TOP_LARGEST, val_shift=0, val_bits=64, n=None,
+        want=("keys", "vals", "pos")):
+    """ebpf_batch_top on host arrays: the ``k`` best entries of ``vals`` (``keys`` beside them, or
+    None) by the field (val_shift, val_bits), largest first, or smallest with TOP_SMALLEST, equal
+    fields by position.  ``n`` (None: every entry) is *n: the table's count, or with TOP_SEGMENTS
+    ebpf_batch_group's info[0].  Returns (keys u64[m], vals u64[m], pos u32[m], info u64[4] = (m,
+    N, the cut, the entries of the cut's field left out)), None where not wanted."""
+    vals = np.ascontiguousarray(vals, dtype=np.uint64)
+    cap = len(vals)
+    if keys is not None:
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        assert len(keys) == cap
+    out = {"keys": np.zeros(k, dtype=np.uint64) if "keys" in want and keys is not None else None,
+           "vals": np.zeros(k, dtype=np.uint64) if "vals" in want else None,
+           "pos": np.zeros(k, dtype=np.uint32) if "pos" in want else None}
+    tops = BatchTops(*[None if out[f] is None else out[f].ctypes.data or 1
+                       for f in ("keys", "vals", "pos")])
+    info = np.zeros(4, dtype=np.uint64)
+    cnt = None if n is None else np.array([n], dtype=np.uint64)
+    _check(lib().ebpf_batch_top(keys.ctypes.data if keys is not None and cap else None,
+                                vals.ctypes.data if cap else None, cap,
+                                None if cnt is None else cnt.ctypes.data, flags, val_shift,
+                                val_bits, k, ctypes.byref(tops), info.ctypes.data),
+           "ebpf_batch_top")
+    m = int(info[0])
+    return tuple(None if out[f] is None else out[f][:m] for f in ("keys", "vals", "pos")) + (info,)
+
+
+def top_dev(device, keys_ptr, vals_ptr, cap, n_ptr, k, info_ptr, flags=TOP_LARGEST, val_shift=0,
+            val_bits=64, keys_out_ptr=None, vals_out_ptr=None, pos_out_ptr=None, stream=None):
+    """ebpf_batch_top_dev: device pointers (ints); the sequence is (keys, vals, cap, n), the outputs
+    that are wanted are given (k entries each: keys_out and vals_out u64, pos_out u32);
+    ``info_ptr`` (4 u64) gets m, N, the cut and the entries of the cut's field left out.
+    Asynchronous on ``stream``."""
+    tops = BatchTops(keys_out_ptr, vals_out_ptr, pos_out_ptr)
+    _check(lib().ebpf_batch_top_dev(device, keys_ptr, vals_ptr, cap, n_ptr, flags, val_shift,
+                                    val_bits, k, ctypes.byref(tops), info_ptr, stream),
+           "ebpf_batch_top_dev")
 
 
 def gather(data, count, index, out_stride=0, stride=0, offsets=None, extents=False,

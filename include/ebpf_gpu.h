@@ -797,6 +797,77 @@ int ebpf_batch_accumulate_dev(int device, const struct ebpf_key_table *in,
 			      uint64_t keep_hi, const struct ebpf_key_table *out, uint64_t *info_dev,
 			      void *stream);
 
+/* The heaviest entries: the k best entries of a keyed sequence by a bit field of its values, found
+ * on the device.  A table of per-flow totals answers "which flows carried the most?", a "last seen"
+ * table "which K flows were idle the longest?" (the K smallest stamps, to evict them), and a few
+ * KB cross to the host instead of the table:
+ *
+ *   tops = {top_keys, top_bytes, NULL};
+ *   ebpf_batch_top_dev(dev, cur.keys, cur.vals, cur.cap, cur.n, EBPF_TOP_LARGEST, 0, 64, 10,
+ *                      &tops, tinfo, s);                (the 10 heaviest flows of the table)
+ *   ebpf_batch_top_dev(dev, group_keys, bytes, group_cap, info, EBPF_TOP_SEGMENTS, 0, 64, 10,
+ *                      &tops, tinfo, s);                (the 10 heaviest flows of this batch)
+ *
+ * Entries: keys and vals have cap entries each, of which N take part.  n NULL: N = cap.  Otherwise
+ *   N = min(*n, cap), the table's rule; with EBPF_TOP_SEGMENTS N is the R of ebpf_batch_reduce (*n
+ *   when *n <= cap, else cap - 1, and 0 for cap == 0), because a reduce that followed a short group
+ *   table left entry cap - 1 unwritten.  So a table plugs in as (t.keys, t.vals, t.cap, t.n), a
+ *   batch as (group_keys, a member of the reduce's sums, group_cap, the group's info) with the
+ *   flag, and any array of counts as (NULL, counts, cap, NULL), each as it stands, after its
+ *   producer on the same stream.  cap is at most 0xffffffff: a position is 32 bits.
+ * Field: f(p) = (vals[p] >> val_shift) & (2^val_bits - 1), 1 <= val_bits <= 64 and val_shift +
+ *   val_bits <= 64, compared as unsigned numbers.  Bits outside the field take no part.
+ * Order: by f descending (EBPF_TOP_LARGEST) or ascending (EBPF_TOP_SMALLEST); entries of equal
+ *   field by ascending position p (for a table: by ascending key).  That is a total order: every
+ *   input has exactly one right answer.
+ * Outputs (struct ebpf_batch_tops): with m = min(k, N) and p_j the j-th position in that order, for
+ *   j < m: keys[j] = keys[p_j], vals[j] = vals[p_j] (the whole word, not the field), pos[j] = p_j.
+ *   Each member is NULL (not wanted: it costs nothing) or has k entries; entries at or past m are
+ *   not written.  keys may be NULL iff out->keys is.  k is at most EBPF_TOP_MAX; k == 0 is valid.
+ *   info (4 entries, always written): info[0] = m; info[1] = N; info[2] = f(p_(m-1)), the cut;
+ *   info[3] = the entries not taken whose field equals the cut, so the cut fell inside a tie iff it
+ *   is not 0.  info[2] and info[3] are 0 for m == 0.  With all three members NULL only info is
+ *   written: the k-th largest or smallest field, a percentile.
+ * The output is a function of the inputs alone: it does not depend on what the outputs held on
+ * entry, and two calls on the same input give the same bytes.  The outputs may not overlap the
+ * inputs or each other.
+ *
+ * ebpf_batch_top: host buffers, a partial sort over positions; no GPU needed (the statement of
+ *   what the device function computes).
+ * ebpf_batch_top_dev: keys_dev, vals_dev, n_dev, the members of *out and info_dev (out itself is a
+ *   host struct) are device memory on `device`; enqueued on `stream` (hipStream_t, NULL = default
+ *   stream), returns without synchronising and never waits for the device.  Every access is
+ *   clamped: nothing outside keys[0 .. N), vals[0 .. N) and *n is read, and nothing outside the
+ *   outputs' [0 .. m) and info[0 .. 4) is written.  The cost follows cap (the kernels are launched
+ *   over it) and val_bits (a pass over the values per 8 bits of the field, and two more), not N or
+ *   k.  Temporary storage is the library's, per stream, shared with ebpf_batch_steer_dev,
+ *   ebpf_batch_group_dev, ebpf_batch_reduce_dev, ebpf_batch_scan_dev, ebpf_batch_filter_dev and
+ *   ebpf_batch_accumulate_dev: 1,040 bytes per 4,096 entries of cap up to 1,024 such tiles (a
+ *   digit's 256 counts and four words), 16 bytes per 4,096 entries past them (the counts are then
+ *   shared by a run of tiles), and 49,216 bytes a call (EBPF_TOP_MAX candidates of 12 bytes).
+ *   Every array is 8-byte aligned, pos 4-byte aligned, as their types say.
+ * Both return 0; EINVAL for a NULL out or info, unknown bits in flags, val_bits outside [1, 64] or
+ * val_shift + val_bits > 64, NULL vals with cap > 0, out->keys given with NULL keys; then E2BIG for
+ * cap above 0xffffffff or k above EBPF_TOP_MAX.  All of these are known on the host, before the
+ * device is looked at.  The device function then returns ENODEV (no GPU, or no such device),
+ * ENOMEM (no scratch) or EIO.  Neither changes the calling thread's current HIP device. */
+#define EBPF_TOP_MAX      4096u  /* k is at most one tile */
+#define EBPF_TOP_LARGEST  0x0u
+#define EBPF_TOP_SMALLEST 0x1u
+#define EBPF_TOP_SEGMENTS 0x2u   /* count the entries by the reduce's rule, not the table's */
+
+struct ebpf_batch_tops {         /* each NULL (not wanted: it costs nothing) or k entries */
+	uint64_t *keys;  /* keys[p_j] */
+	uint64_t *vals;  /* vals[p_j], the whole word, not the field */
+	uint32_t *pos;   /* p_j */
+};
+int ebpf_batch_top(const uint64_t *keys, const uint64_t *vals, uint64_t cap, const uint64_t *n,
+		   uint32_t flags, uint32_t val_shift, uint32_t val_bits, uint64_t k,
+		   const struct ebpf_batch_tops *out, uint64_t *info);
+int ebpf_batch_top_dev(int device, const uint64_t *keys_dev, const uint64_t *vals_dev, uint64_t cap,
+		       const uint64_t *n_dev, uint32_t flags, uint32_t val_shift, uint32_t val_bits,
+		       uint64_t k, const struct ebpf_batch_tops *out, uint64_t *info_dev, void *stream);
+
 /* Gathering packets into a dense batch: a list of n packets of `batch` (a class of a steered
  * batch, the whole steering index, any list of the caller's own: duplicates and any order are
  * fine) copied, in list order, into `out`.  A class can then leave the device on its own (a TX
