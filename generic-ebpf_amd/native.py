@@ -100,6 +100,14 @@ class KeyTable(ctypes.Structure):
                 ("n", ctypes.c_void_p)]
 
 
+class BatchRolls(ctypes.Structure):
+    """struct ebpf_batch_rolls: the outputs of a rollup call, each NULL or out_cap entries (starts
+    out_cap + 1)"""
+    _fields_ = [("keys", ctypes.c_void_p), ("count", ctypes.c_void_p), ("sum", ctypes.c_void_p),
+                ("min", ctypes.c_void_p), ("max", ctypes.c_void_p), ("bits", ctypes.c_void_p),
+                ("starts", ctypes.c_void_p)]
+
+
 class BatchTops(ctypes.Structure):
     """struct ebpf_batch_tops: the outputs of a top call, each NULL or k entries"""
     _fields_ = [("keys", ctypes.c_void_p), ("vals", ctypes.c_void_p), ("pos", ctypes.c_void_p)]
@@ -183,6 +191,9 @@ FUNCS = {
     "ebpf_batch_accumulate": (_I, [_VP, _VP, _VP, _U64, _VP, _U32, _U64, _U64, _VP, _VP]),
     "ebpf_batch_accumulate_dev": (_I, [_I, _VP, _VP, _VP, _U64, _VP, _U32, _U64, _U64, _VP, _VP,
                                        _VP]),
+    "ebpf_batch_rollup": (_I, [_VP, _VP, _U64, _VP, _U32, _U32, _U32, _U32, _U64, _VP, _VP]),
+    "ebpf_batch_rollup_dev": (_I, [_I, _VP, _VP, _U64, _VP, _U32, _U32, _U32, _U32, _U64, _VP, _VP,
+                                   _VP]),
     "ebpf_batch_top": (_I, [_VP, _VP, _U64, _VP, _U32, _U32, _U32, _U64, _VP, _VP]),
     "ebpf_batch_top_dev": (_I, [_I, _VP, _VP, _U64, _VP, _U32, _U32, _U32, _U64, _VP, _VP, _VP]),
     "ebpf_batch_gather": (_I, [_VP, _VP, _U64, _U32, _VP, _U64, _VP]),
@@ -206,6 +217,8 @@ STEER_TILE = 4096           # csrc/host/steer.h STEER_TILE: packets per workgrou
 EBPF_NO_ENTRY = 0xffffffff  # EBPF_NO_ENTRY: the position of a key that a table does not hold
 LOOKUP_VALUE, LOOKUP_REMAINING = 0, 1          # EBPF_LOOKUP_*: the modes of a lookup
 ACC_ADD, ACC_MIN, ACC_MAX, ACC_OR = range(4)   # EBPF_ACC_*: the ops of an accumulate
+ROLLUP_SEGMENTS = 1                            # EBPF_ROLLUP_SEGMENTS: N by the reduce's rule
+ROLLS = ("keys", "count", "sum", "min", "max", "bits", "starts")   # ebpf_batch_rolls' members
 TOP_MAX = 4096                                 # EBPF_TOP_MAX: the most entries a top call takes
 TOP_LARGEST, TOP_SMALLEST, TOP_SEGMENTS = 0, 1, 2   # EBPF_TOP_*: the flags of a top call
 
@@ -955,6 +968,53 @@ def accumulate_dev(device, in_table, keys_ptr, adds_ptr, key_cap, out_table, inf
                                            keys_ptr, adds_ptr, key_cap, nkeys_ptr, op, keep_lo,
                                            keep_hi, ctypes.byref(tout), info_ptr, stream),
            "ebpf_batch_accumulate_dev")
+
+
+def rollup(keys, vals, key_shift, flags=0, val_shift=0, val_bits=64, out_cap=None, n=None,
+           want=ROLLS):
+    """ebpf_batch_rollup on host arrays: the runs of equal ``key >> key_shift`` of ``keys`` reduced
+    (``vals`` beside them, or None when no output of ``want`` reads them: sum, min, max, bits).
+    ``n`` (None: every entry) is *n: the table's count, or with ROLLUP_SEGMENTS ebpf_batch_group's
+    info[0].  ``out_cap`` (None: room for every run) is the outputs' size.  Returns ({member: u64
+    array of the min(C, out_cap) entries written; starts one more when C <= out_cap}, info u64[2]
+    = (C, N), code) with the members not wanted absent; code is 0 or errno.ENOSPC for C >
+    out_cap."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    cap = len(keys)
+    if vals is not None:
+        vals = np.ascontiguousarray(vals, dtype=np.uint64)
+        assert len(vals) == cap
+    want = tuple(w for w in ROLLS if w in want and
+                 (vals is not None or w not in ("sum", "min", "max", "bits")))
+    if out_cap is None:
+        out_cap = cap
+    out = {w: np.zeros(out_cap + (w == "starts"), dtype=np.uint64) for w in want}
+    rolls = BatchRolls(*[out[w].ctypes.data or 1 if w in out else None for w in ROLLS])
+    info = np.zeros(2, dtype=np.uint64)
+    cnt = None if n is None else np.array([n], dtype=np.uint64)
+    code = lib().ebpf_batch_rollup(keys.ctypes.data if cap else None,
+                                   vals.ctypes.data if vals is not None and cap else None, cap,
+                                   None if cnt is None else cnt.ctypes.data, flags, key_shift,
+                                   val_shift, val_bits, out_cap, ctypes.byref(rolls),
+                                   info.ctypes.data)
+    if code not in (0, errno.ENOSPC):
+        raise EbpfError(code, "ebpf_batch_rollup")
+    C = int(info[0])
+    m = min(C, out_cap)
+    return ({w: out[w][:m + (w == "starts" and C <= out_cap)] for w in want}, info, code)
+
+
+def rollup_dev(device, keys_ptr, vals_ptr, cap, n_ptr, key_shift, out_cap, info_ptr, flags=0,
+               val_shift=0, val_bits=64, keys_out_ptr=None, count_ptr=None, sum_ptr=None,
+               min_ptr=None, max_ptr=None, bits_ptr=None, starts_ptr=None, stream=None):
+    """ebpf_batch_rollup_dev: device pointers (ints); the sequence is (keys, vals, cap, n), the
+    outputs that are wanted are given (out_cap u64 each, starts out_cap + 1); ``info_ptr`` (2 u64)
+    gets C and N.  Asynchronous on ``stream``."""
+    rolls = BatchRolls(keys_out_ptr, count_ptr, sum_ptr, min_ptr, max_ptr, bits_ptr, starts_ptr)
+    _check(lib().ebpf_batch_rollup_dev(device, keys_ptr, vals_ptr, cap, n_ptr, flags, key_shift,
+                                       val_shift, val_bits, out_cap, ctypes.byref(rolls), info_ptr,
+                                       stream),
+           "ebpf_batch_rollup_dev")
 
 
 def top(keys, vals, k, flags=TOP_LARGEST, val_shift=0, val_bits=64, n=None,

@@ -797,6 +797,97 @@ int ebpf_batch_accumulate_dev(int device, const struct ebpf_key_table *in,
 			      uint64_t keep_hi, const struct ebpf_key_table *out, uint64_t *info_dev,
 			      void *stream);
 
+/* Rolling a table up: the entries of a keyed sequence reduced per key prefix, on the device.  The
+ * tables above answer per exact key; the question is often one level up.  With dst << 32 | src as
+ * the key, the entries under one dst are the distinct sources that reached it; a table of bytes
+ * per host gives bytes per /24.  The keys are sorted, so the entries that share a prefix lie in one
+ * run, and the result is again a sorted table: it goes to the top, a lookup, an accumulate or a
+ * second rollup, on the same stream:
+ *
+ *   rolls = {dsts, nsrc, bytes, NULL, NULL, NULL, NULL};
+ *   ebpf_batch_rollup_dev(dev, cur.keys, cur.vals, cur.cap, cur.n, 0, 32, 0, 64, out_cap, &rolls,
+ *                         rinfo, s);           (per dst: its distinct sources, its bytes)
+ *   ebpf_batch_top_dev(dev, dsts, nsrc, out_cap, rinfo, EBPF_TOP_LARGEST, 0, 64, 10, &tops, tinfo,
+ *                      s);                     (the 10 destinations with the most sources)
+ *   ebpf_batch_rollup_dev(dev, group_keys, bytes, group_cap, info, EBPF_ROLLUP_SEGMENTS, 8, 0, 64,
+ *                         out_cap, &rolls, rinfo, s);     (this batch's hosts, per /24)
+ *
+ * Entries: ebpf_batch_top's rule.  keys and vals have cap entries each, of which N take part.
+ *   n NULL: N = cap.  Otherwise N = min(*n, cap), the table's rule; with EBPF_ROLLUP_SEGMENTS N is
+ *   the R of ebpf_batch_reduce (*n when *n <= cap, else cap - 1, and 0 for cap == 0).  So a table
+ *   plugs in as (t.keys, t.vals, t.cap, t.n), a batch as (group_keys, a member of the reduce's
+ *   sums, group_cap, the group's info) with the flag, each as it stands, after its producer on the
+ *   same stream.  cap is at most 0xffffffff: a position is 32 bits.
+ * Prefix: c(p) = keys[p] >> key_shift, 0 <= key_shift <= 63.  key_shift 0 is legal: over strictly
+ *   ascending keys every entry is then its own run.
+ * Runs: a run is a maximal stretch of adjacent positions of [0, N) with equal c: position p begins
+ *   a run iff p == 0 or c(p) != c(p - 1).  That is defined for any keys, sorted or not, and neither
+ *   function refuses any.  The output keys are strictly ascending, so that the output is a table,
+ *   iff the input keys are non-decreasing.  C is the number of runs.
+ * Value: v(p) = (vals[p] >> val_shift) & (2^val_bits - 1), 1 <= val_bits <= 64 and val_shift +
+ *   val_bits <= 64, the reduce's field.  vals may be NULL iff sum, min, max and bits all are; the
+ *   field is checked only when vals is used.
+ * Outputs (struct ebpf_batch_rolls): each member is NULL (not wanted: it costs nothing) or has
+ *   out_cap entries, starts out_cap + 1.  For run r < min(C, out_cap), of positions [a, b):
+ *     keys[r] = c(a); count[r] = b - a (for a table: the distinct keys under the prefix);
+ *     sum[r], min[r], max[r], bits[r] = the sum modulo 2^64, the smallest, the largest (unsigned)
+ *       and the OR of v over [a, b);
+ *     starts[r] = a.
+ *   Entries at or past min(C, out_cap) are not written, but starts[C] = N is, iff C <= out_cap (the
+ *   group table's rule: run r is positions [starts[r], starts[r + 1])).  Every run is reduced
+ *   whole even when the outputs are short, so short outputs are a table by the table's rule: its
+ *   first out_cap entries.
+ *   info (2 entries, always written): info[0] = C even when C > out_cap (snprintf's rule: the
+ *   outputs are complete iff info[0] <= out_cap); info[1] = N.  So (out->keys, out->count or
+ *   out->sum ..., out_cap, info) is an ebpf_key_table with n = info.
+ *   N == 0: info = {0, 0} and starts[0] = 0.  With all members NULL only info is written: the
+ *   number of prefixes.  out_cap == 0 is legal, with members or without: nothing but info (and
+ *   starts[0] for N == 0) is written.
+ * The output is a function of the inputs alone: it does not depend on what the outputs held on
+ * entry, and two calls on the same input give the same bytes.  The outputs may not overlap the
+ * inputs or each other.
+ *
+ * ebpf_batch_rollup: host buffers, one pass; no GPU needed (the statement of what the device
+ *   function computes).  It returns ENOSPC when C > out_cap, with everything that fits and info
+ *   written, as ebpf_batch_group does.
+ * ebpf_batch_rollup_dev: keys_dev, vals_dev, n_dev, the members of *out and info_dev (out itself
+ *   is a host struct) are device memory on `device`, 8-byte aligned; enqueued on `stream`
+ *   (hipStream_t, NULL = default stream), returns without synchronising and never waits for the
+ *   device.  Short outputs return 0: the caller compares info[0] with out_cap after the stream.
+ *   Every access is clamped: nothing outside keys[0 .. N), vals[0 .. N) and *n is read, and nothing
+ *   outside the members' [0, min(C, out_cap)), starts[0 .. min(C, out_cap)] (its last entry only
+ *   when C <= out_cap) and info[0 .. 2) is written.  The cost follows cap (the kernels are launched
+ *   over it), not N, C or the lengths of the runs.  Temporary storage is the library's, per stream,
+ *   shared with ebpf_batch_steer_dev, ebpf_batch_group_dev, ebpf_batch_reduce_dev,
+ *   ebpf_batch_scan_dev, ebpf_batch_filter_dev, ebpf_batch_accumulate_dev and ebpf_batch_top_dev:
+ *   128 bytes per 4,096 entries of cap (a tile's runs and what is open at its edges), at least 128
+ *   bytes a call.
+ * Both return 0; EINVAL for a NULL out or info, unknown bits in flags, key_shift above 63, and,
+ * when an output reads the values, val_bits outside [1, 64] or val_shift + val_bits > 64; EINVAL
+ * for NULL keys with cap > 0, and for NULL vals with cap > 0 when an output reads the values; then
+ * E2BIG for cap or out_cap above 0xffffffff.  All of these are known on the host, before the
+ * device is looked at, and nothing is written.  The device function then returns ENODEV (no GPU,
+ * or no such device), ENOMEM (no scratch) or EIO.  Neither changes the calling thread's current
+ * HIP device. */
+#define EBPF_ROLLUP_SEGMENTS 0x1u   /* count the input's entries by the reduce's rule, not the table's */
+
+struct ebpf_batch_rolls {      /* each NULL (not wanted: it costs nothing) */
+	uint64_t *keys;    /* out_cap entries: the run's prefix, keys[p] >> key_shift            */
+	uint64_t *count;   /* out_cap entries: the entries of the run (the distinct keys below it) */
+	uint64_t *sum;     /* out_cap entries: sum of the value field, modulo 2^64               */
+	uint64_t *min;     /* out_cap entries: smallest value field, unsigned                    */
+	uint64_t *max;     /* out_cap entries: largest value field, unsigned                     */
+	uint64_t *bits;    /* out_cap entries: OR of the value fields                            */
+	uint64_t *starts;  /* out_cap + 1 entries: the run's first position in the input         */
+};
+int ebpf_batch_rollup(const uint64_t *keys, const uint64_t *vals, uint64_t cap, const uint64_t *n,
+		      uint32_t flags, uint32_t key_shift, uint32_t val_shift, uint32_t val_bits,
+		      uint64_t out_cap, const struct ebpf_batch_rolls *out, uint64_t *info);
+int ebpf_batch_rollup_dev(int device, const uint64_t *keys_dev, const uint64_t *vals_dev,
+			  uint64_t cap, const uint64_t *n_dev, uint32_t flags, uint32_t key_shift,
+			  uint32_t val_shift, uint32_t val_bits, uint64_t out_cap,
+			  const struct ebpf_batch_rolls *out, uint64_t *info_dev, void *stream);
+
 /* The heaviest entries: the k best entries of a keyed sequence by a bit field of its values, found
  * on the device.  A table of per-flow totals answers "which flows carried the most?", a "last seen"
  * table "which K flows were idle the longest?" (the K smallest stamps, to evict them), and a few
