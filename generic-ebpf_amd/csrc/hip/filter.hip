@@ -167,9 +167,8 @@ filter_tiles(tests t, uint64_t val_mask, uint64_t count, const uint32_t *__restr
 		counts[blockIdx.x] = (uint32_t)total;
 }
 
-// One workgroup: a thread walks its run of tiles (run_of) twice, first for its run's total, then,
-// with the totals of the threads before it, to leave in every tile's word the passing positions
-// of the tiles before.  K <= n < 2^32: 32-bit sums.
+// One workgroup: tile_counts_scan leaves in every tile's word the passing positions of the tiles
+// before.  K <= n < 2^32: 32-bit sums.
 __global__ void __launch_bounds__(CARRY_THREADS)
 filter_carry(uint32_t *__restrict__ scratch, uint32_t ntiles, uint64_t n,
 	     const uint64_t *__restrict__ S, uint64_t cap, const uint64_t *__restrict__ nseg,
@@ -177,17 +176,7 @@ filter_carry(uint32_t *__restrict__ scratch, uint32_t ntiles, uint64_t n,
 {
 	__shared__ uint32_t wsum[CARRY_THREADS / 64];
 	uint32_t *counts = scratch + FILTER_HEAD_WORDS;
-	const auto [t0, t1] = run_of(ntiles);
-	uint32_t mine = 0;
-	for (uint32_t t = t0; t < t1; t++)
-		mine += counts[t];
-	uint32_t all;
-	uint32_t cur = block_scan<CARRY_THREADS / 64>(mine, wsum, all);
-	for (uint32_t t = t0; t < t1; t++) {
-		const uint32_t own = counts[t];
-		counts[t] = cur;
-		cur += own;
-	}
+	const uint32_t all = tile_counts_scan(counts, counts, 1, ntiles, wsum);
 	if (threadIdx.x == 0) {
 		const cover c = cover_of(S, cap, nseg, n);
 		scratch[0] = all;
@@ -305,13 +294,6 @@ filter_place(const uint32_t *__restrict__ scratch, uint32_t ntiles,
 		if (out.dropped_starts != nullptr)
 			out.dropped_starts[g] = D;
 	}
-}
-
-uint32_t
-tiles_of(uint64_t n)
-{
-	const uint64_t t = (n + TILE - 1) / TILE;
-	return t != 0 ? (uint32_t)t : 1;
 }
 
 } // namespace

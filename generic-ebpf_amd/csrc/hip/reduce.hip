@@ -42,14 +42,15 @@ typedef struct ebpf_batch_sums sums;
 // A run of list entries reduced: of segment g if flag, else of the segment that was open before
 // the run began.
 struct part {
-	uint64_t bytes, sum, mn, mx, bits;
+	uint64_t bytes;
+	stats s;
 	uint32_t g, flag;
 };
 
 __device__ __forceinline__ part
 nothing()
 {
-	return {0, 0, ~0ull, 0, 0, 0, 0};
+	return {0, NO_STATS, 0, 0};
 }
 
 // a's entries, then b's, of one segment
@@ -59,12 +60,8 @@ add(part &a, const part &b)
 {
 	if (LENS)
 		a.bytes += b.bytes;
-	if (VALS) {
-		a.sum += b.sum;
-		a.mn = b.mn < a.mn ? b.mn : a.mn;
-		a.mx = b.mx > a.mx ? b.mx : a.mx;
-		a.bits |= b.bits;
-	}
+	if (VALS)
+		add(a.s, b.s);
 }
 
 // The segmented scan's operator: run a, then run b.  A segment that begins in b closes a.
@@ -88,12 +85,8 @@ lane_up(const part &p, uint32_t d)
 	r.flag = __shfl_up(p.flag, d);
 	if (LENS)
 		r.bytes = __shfl_up((unsigned long long)p.bytes, d);
-	if (VALS) {
-		r.sum = __shfl_up((unsigned long long)p.sum, d);
-		r.mn = __shfl_up((unsigned long long)p.mn, d);
-		r.mx = __shfl_up((unsigned long long)p.mx, d);
-		r.bits = __shfl_up((unsigned long long)p.bits, d);
-	}
+	if (VALS)
+		r.s = up(p.s, d);
 	return r;
 }
 
@@ -103,12 +96,8 @@ store_row(uint64_t *__restrict__ row, const part &p)
 {
 	if (LENS)
 		row[0] = p.bytes;
-	if (VALS) {
-		row[1] = p.sum;
-		row[2] = p.mn;
-		row[3] = p.mx;
-		row[4] = p.bits;
-	}
+	if (VALS)
+		store(row + 1, p.s);
 }
 
 template <bool LENS, bool VALS>
@@ -118,12 +107,8 @@ load_row(const uint64_t *__restrict__ row)
 	part p = nothing();
 	if (LENS)
 		p.bytes = row[0];
-	if (VALS) {
-		p.sum = row[1];
-		p.mn = row[2];
-		p.mx = row[3];
-		p.bits = row[4];
-	}
+	if (VALS)
+		p.s = load(row + 1);
 	return p;
 }
 
@@ -138,30 +123,18 @@ write_out(const sums &out, uint64_t g, uint64_t R, const part &p)
 		out.bytes[g] = p.bytes;
 	if (VALS) {
 		if (out.sum != nullptr)
-			out.sum[g] = p.sum;
+			out.sum[g] = p.s.sum;
 		if (out.min != nullptr)
-			out.min[g] = p.mn;
+			out.min[g] = p.s.mn;
 		if (out.max != nullptr)
-			out.max[g] = p.mx;
+			out.max[g] = p.s.mx;
 		if (out.bits != nullptr)
-			out.bits[g] = p.bits;
+			out.bits[g] = p.s.bits;
 	}
 }
 
-// One statistic on its own: 0 bytes, 1 sum, 2 min, 3 max, 4 bits.
-template <int STAT>
-__device__ __forceinline__ uint64_t
-ident()
-{
-	return STAT == 2 ? ~0ull : 0;
-}
-
-template <int STAT>
-__device__ __forceinline__ uint64_t
-fold(uint64_t a, uint64_t b)
-{
-	return STAT <= 1 ? a + b : STAT == 2 ? (b < a ? b : a) : STAT == 3 ? (b > a ? b : a) : a | b;
-}
+// the one output beside the four statistics of seg_tile.h: a sum
+enum { BYTES = STATS };
 
 // One output of the segments that a tile closes, written in segment order: the tile's e-th
 // marked position closes the segment that the one before it began, number sg[e - 1].  The thread
@@ -191,7 +164,7 @@ write_staged(uint64_t *__restrict__ dst, uint64_t R, const uint32_t (&seg)[PER_T
 				acc = ident<STAT>();
 				e++;
 			}
-			acc = fold<STAT>(acc, STAT == 0 ? len[k] : has[k] ? val[k] : ident<STAT>());
+			acc = fold<STAT>(acc, STAT == BYTES ? len[k] : has[k] ? val[k] : ident<STAT>());
 		}
 		__syncthreads();
 		const uint32_t m = closed - base < STAGE ? closed - base : STAGE;
@@ -282,7 +255,7 @@ reduce_tiles(places f, const uint64_t *__restrict__ ret, uint32_t val_shift, uin
 		if (LENS)
 			p.bytes = len[k];
 		if (VALS && has[k])
-			p.sum = p.mn = p.mx = p.bits = val[k];
+			p.s = {val[k], val[k], val[k], val[k]};
 		return p;
 	};
 	// what leaves the thread on its right: its last run
@@ -317,12 +290,12 @@ reduce_tiles(places f, const uint64_t *__restrict__ ret, uint32_t val_shift, uin
 			if (seg[k] != NOHEAD)
 				sg[e++] = seg[k];
 		if (LENS)
-			write_staged<0>(out.bytes, R, seg, len, val, has, cur.bytes, hb, closed, sg, sv);
+			write_staged<BYTES>(out.bytes, R, seg, len, val, has, cur.bytes, hb, closed, sg, sv);
 		if (VALS) {
-			write_staged<1>(out.sum, R, seg, len, val, has, cur.sum, hb, closed, sg, sv);
-			write_staged<2>(out.min, R, seg, len, val, has, cur.mn, hb, closed, sg, sv);
-			write_staged<3>(out.max, R, seg, len, val, has, cur.mx, hb, closed, sg, sv);
-			write_staged<4>(out.bits, R, seg, len, val, has, cur.bits, hb, closed, sg, sv);
+			write_staged<SUM>(out.sum, R, seg, len, val, has, cur.s.sum, hb, closed, sg, sv);
+			write_staged<MIN>(out.min, R, seg, len, val, has, cur.s.mn, hb, closed, sg, sv);
+			write_staged<MAX>(out.max, R, seg, len, val, has, cur.s.mx, hb, closed, sg, sv);
+			write_staged<BITS>(out.bits, R, seg, len, val, has, cur.s.bits, hb, closed, sg, sv);
 		}
 	}
 #pragma unroll
@@ -432,9 +405,7 @@ launch_reduce(const struct ebpf_pkt_batch *batch, const uint64_t *ret, uint64_t 
 	      const uint64_t *seg_starts, uint64_t seg_cap, const uint64_t *nseg,
 	      const struct ebpf_batch_sums &out, uint64_t *scratch, hipStream_t stream)
 {
-	const bool lens = out.bytes != nullptr;
-	const bool vals = out.sum != nullptr || out.min != nullptr || out.max != nullptr ||
-			  out.bits != nullptr;
+	const bool lens = out.bytes != nullptr, vals = wants_values(out);
 	if (n != 0) {
 		const places f = lens ? places_of(*batch) : places{nullptr, count, 0, 0};
 		const bit_field vf = field_of(val_shift, val_bits);

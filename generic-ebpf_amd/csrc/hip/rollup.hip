@@ -48,20 +48,10 @@ struct roll_args {
 	bit_field f;
 };
 
-// N, the entries that take part: the table's rule, or the reduce's
-__device__ __forceinline__ uint64_t
-entries_of(const roll_args &a)
-{
-	if (a.segments)
-		return segments_of(a.cap, a.n);
-	if (a.n == nullptr)
-		return a.cap;
-	const uint64_t n = *a.n;
-	return n < a.cap ? n : a.cap;
-}
-
 // A stretch of entries reduced: of the run that begins at `start` if flag, else of the run that
-// was open before the stretch began.
+// was open before the stretch began.  (The four values are written out here and not seg_tile.h's
+// stats record as reduce.hip has it: as a member it moved rollup_carry<true>'s registers, and a
+// line of tools/rollup_bench.py left the parent's spread; profiles/keyed_refactor.)
 struct part {
 	uint64_t sum, mn, mx, bits;
 	uint32_t start, flag;
@@ -79,29 +69,14 @@ begins_at(uint64_t p)
 	return {0, ~0ull, 0, 0, (uint32_t)p, 1};
 }
 
-// a's entries, then b's, of one run
-template <bool VALS>
+// a's values, then b's, of one run
 __device__ __forceinline__ void
-add(part &a, const part &b)
+add_stats(part &a, const part &b)
 {
-	if (VALS) {
-		a.sum += b.sum;
-		a.mn = b.mn < a.mn ? b.mn : a.mn;
-		a.mx = b.mx > a.mx ? b.mx : a.mx;
-		a.bits |= b.bits;
-	}
-}
-
-template <bool VALS>
-__device__ __forceinline__ void
-add_value(part &a, uint64_t v)
-{
-	if (VALS) {
-		a.sum += v;
-		a.mn = v < a.mn ? v : a.mn;
-		a.mx = v > a.mx ? v : a.mx;
-		a.bits |= v;
-	}
+	a.sum += b.sum;
+	a.mn = b.mn < a.mn ? b.mn : a.mn;
+	a.mx = b.mx > a.mx ? b.mx : a.mx;
+	a.bits |= b.bits;
 }
 
 // The segmented scan's operator: stretch a, then stretch b.  A run that begins in b closes a.
@@ -112,7 +87,8 @@ join(const part &a, const part &b)
 	if (b.flag)
 		return b;
 	part r = a;
-	add<VALS>(r, b);
+	if (VALS)
+		add_stats(r, b);
 	return r;
 }
 
@@ -174,18 +150,9 @@ load_tile(const roll_args &a, uint64_t N, uint64_t first, uint64_t *buf, owned &
 {
 	const uint32_t tid = threadIdx.x;
 	uint64_t x[PER_THREAD], y[PER_THREAD];
-#pragma unroll
-	for (uint32_t k = 0; k < PER_THREAD; k++) {
-		const uint64_t e = first + k * THREADS + tid;
-		x[k] = e < N ? a.keys[e] : 0;
-	}
-	if (VALS) {
-#pragma unroll
-		for (uint32_t k = 0; k < PER_THREAD; k++) {
-			const uint64_t e = first + k * THREADS + tid;
-			y[k] = e < N ? a.vals[e] : 0;
-		}
-	}
+	strided_of(a.keys, N, first, x);
+	if (VALS)
+		strided_of(a.vals, N, first, y);
 	// the entry before the thread's: before the tile (thread 0), or its neighbour's last
 	uint64_t prev = 0;
 	if (tid == 0 && first != 0)
@@ -227,8 +194,13 @@ template <bool VALS>
 __device__ __forceinline__ void
 add_entry(part &a, const owned &r, uint32_t k)
 {
-	if (r.has >> k & 1)
-		add_value<VALS>(a, r.val[k]);
+	if (VALS && (r.has >> k & 1)) {
+		const uint64_t v = r.val[k];
+		a.sum += v;
+		a.mn = v < a.mn ? v : a.mn;
+		a.mx = v > a.mx ? v : a.mx;
+		a.bits |= v;
+	}
 }
 
 // what leaves the thread on its right: its last run, or all its entries if none begins in it
@@ -255,7 +227,7 @@ rollup_tiles(roll_args a, uint64_t *__restrict__ scratch)
 	__shared__ uint64_t wsum[WAVES];
 	const uint32_t tid = threadIdx.x;
 	uint64_t *row = scratch + (size_t)blockIdx.x * ROW;
-	const uint64_t N = entries_of(a), first = (uint64_t)blockIdx.x * TILE;
+	const uint64_t N = entries_of(a.cap, a.n, a.segments), first = (uint64_t)blockIdx.x * TILE;
 	if (first >= N) { // (the same for every thread)
 		if (tid == 0) {
 			row[0] = 0;
@@ -335,7 +307,7 @@ rollup_carry(roll_args a, uint32_t ntiles, uint64_t out_cap, uint64_t *__restric
 		cur = join<VALS>(cur, tile_tail<VALS>(row));
 	}
 	if (threadIdx.x == 0) {
-		const uint64_t N = entries_of(a);
+		const uint64_t N = entries_of(a.cap, a.n, a.segments);
 		info[0] = C;
 		info[1] = N;
 		if (starts != nullptr && C <= out_cap)
@@ -350,23 +322,9 @@ struct placing {
 	bool last;                        // the tile holds entry N - 1
 };
 
-// One output: 0 keys and 1 starts are an entry's that begins a run, the others of the run that
-// such an entry closes.
-enum { KEYS, STARTS, COUNT, SUM, MIN, MAX, BITS };
-
-template <int STAT>
-__device__ __forceinline__ uint64_t
-ident()
-{
-	return STAT == MIN ? ~0ull : 0;
-}
-
-template <int STAT>
-__device__ __forceinline__ uint64_t
-fold(uint64_t a, uint64_t b)
-{
-	return STAT == SUM ? a + b : STAT == MIN ? (b < a ? b : a) : STAT == MAX ? (b > a ? b : a) : a | b;
-}
+// One output: the four statistics (seg_tile.h) and the count are of the run that an entry which
+// begins a run closes, keys and starts are that entry's own.
+enum { COUNT = STATS, KEYS, STARTS };
 
 // One output of the tile, written in run order through sv: the tile's e-th entry that begins a
 // run is run base + e, and closes run base + e - 1 (none for the sequence's first entry); the last
@@ -379,7 +337,7 @@ stage(uint64_t *__restrict__ dst, const placing &t, const owned &r, const part &
 {
 	if (dst == nullptr) // (the same for every thread)
 		return;
-	constexpr bool closes = STAT >= COUNT;
+	constexpr bool closes = STAT <= COUNT;
 	const uint32_t tid = threadIdx.x;
 	uint64_t acc = STAT == SUM ? in.sum : STAT == MIN ? in.mn : STAT == MAX ? in.mx : in.bits;
 	uint64_t start = in.start;
@@ -392,7 +350,7 @@ stage(uint64_t *__restrict__ dst, const placing &t, const owned &r, const part &
 			acc = ident<STAT>();
 			start = p;
 		}
-		if (STAT >= SUM)
+		if (STAT < STATS)
 			acc = fold<STAT>(acc, r.has >> k & 1 ? r.val[k] : ident<STAT>());
 	}
 	if (closes && t.last && tid == THREADS - 1)
@@ -415,7 +373,7 @@ rollup_place(roll_args a, uint64_t out_cap, rolls out, const uint64_t *__restric
 	__shared__ part wtot[WAVES];
 	__shared__ uint64_t wsum[WAVES];
 	const uint64_t *row = scratch + (size_t)blockIdx.x * ROW;
-	const uint64_t N = entries_of(a), first = (uint64_t)blockIdx.x * TILE;
+	const uint64_t N = entries_of(a.cap, a.n, a.segments), first = (uint64_t)blockIdx.x * TILE;
 	if (first >= N) // (the same for every thread)
 		return;
 	owned r;
@@ -429,7 +387,8 @@ rollup_place(roll_args a, uint64_t out_cap, rolls out, const uint64_t *__restric
 	if (!cur.flag) {
 		in = load_vals<VALS>(row + 11);
 		in.start = (uint32_t)row[15];
-		add<VALS>(in, cur);
+		if (VALS)
+			add_stats(in, cur);
 	}
 	const placing t = {first, N, row[1], out_cap, hb, (uint32_t)all, N - first <= TILE};
 	// (buf is free: every thread has its entries in registers, and barriers lie between)
@@ -442,13 +401,6 @@ rollup_place(roll_args a, uint64_t out_cap, rolls out, const uint64_t *__restric
 		stage<MAX>(out.max, t, r, in, buf);
 		stage<BITS>(out.bits, t, r, in, buf);
 	}
-}
-
-uint32_t
-tiles_of(uint64_t n)
-{
-	const uint64_t t = (n + TILE - 1) / TILE;
-	return t != 0 ? (uint32_t)t : 1;
 }
 
 } // namespace
@@ -465,8 +417,7 @@ launch_rollup(const uint64_t *keys, const uint64_t *vals, uint64_t cap, const ui
 	      uint64_t out_cap, const rolls &out, uint64_t *info, uint64_t *scratch, hipStream_t stream)
 {
 	const uint32_t ntiles = tiles_of(cap);
-	const bool values = out.sum != nullptr || out.min != nullptr || out.max != nullptr ||
-			    out.bits != nullptr;
+	const bool values = wants_values(out);
 	const bool wanted = values || out.keys != nullptr || out.count != nullptr || out.starts != nullptr;
 	const roll_args a = {keys, values ? vals : nullptr, cap, n, flags & EBPF_ROLLUP_SEGMENTS ? 1u : 0u,
 			     key_shift, values ? field_of(val_shift, val_bits) : field_of(0, 64)};

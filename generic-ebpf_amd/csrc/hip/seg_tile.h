@@ -1,7 +1,10 @@
-// seg_tile.h — what the segmented list kernels share (reduce.hip, scan.hip, filter.hip): the tile
-// shape, a list's segments (their number, bounds and end, the 64-way search), a tile's LDS slots,
-// a thread's lengths and values, the segmented scan over a workgroup's threads, a carry thread's
-// run of tiles, and run-time flags as template arguments.  Device code but for with_flags; every
+// seg_tile.h — what the segmented list kernels (reduce.hip, scan.hip, filter.hip) and the
+// keyed-sequence kernels (table.hip, top.hip, rollup.hip) share: the tile shape and the tiles of a
+// sequence, a list's segments (their number, bounds and end, the 64-way search) and a sequence's
+// entries, a tile's LDS slots, a thread's lengths and values and its strided entries, a tile's
+// ballot words and a wave's scan of their counts, the segmented scan over a workgroup's threads, a
+// carry thread's run of tiles and the carry scan of the tiles' counts, the sum/min/max/OR record,
+// and run-time flags as template arguments.  Device code but for tiles_of and with_flags; every
 // file that includes it is compiled on its own: everything here is file-local.
 #pragma once
 #include <type_traits>
@@ -18,6 +21,14 @@ constexpr uint32_t CARRY_THREADS = 1024; // a carry kernel's one workgroup
 constexpr uint32_t NOHEAD = ~0u;         // no segment begins here (a segment's number is below it)
 static_assert(PER_THREAD == 16, "a thread's positions are one padded LDS row, and 16 bits");
 
+// The tiles of n entries, at least one: a launcher's grid, and its scratch.
+inline uint32_t
+tiles_of(uint64_t n)
+{
+	const uint64_t t = (n + TILE - 1) / TILE;
+	return t != 0 ? (uint32_t)t : 1;
+}
+
 // The number of segments of a list (ebpf_gpu.h): a short table holds no end for its last group.
 // (host/list_args.h seg_count is the host's statement of the rule.)
 __device__ __forceinline__ uint64_t
@@ -27,6 +38,19 @@ segments_of(uint64_t cap, const uint64_t *__restrict__ nseg)
 		return cap;
 	const uint64_t g = *nseg;
 	return g <= cap ? g : (cap != 0 ? cap - 1 : 0);
+}
+
+// The entries of a keyed sequence that take part (ebpf_gpu.h): the reduce's rule above, or the
+// table's, a short sequence being its first cap entries.  (host/list_args.h entry_count.)
+__device__ __forceinline__ uint64_t
+entries_of(uint64_t cap, const uint64_t *__restrict__ n, uint32_t segments)
+{
+	if (segments)
+		return segments_of(cap, n);
+	if (n == nullptr)
+		return cap;
+	const uint64_t v = *n;
+	return v < cap ? v : cap;
 }
 
 // Segment g's positions [a, b), clamped to the list.
@@ -119,6 +143,46 @@ fields_of(const places &f, const uint64_t *__restrict__ ret, bit_field vf, const
 	}
 }
 
+// A thread's entries first + k * THREADS + tid of a[0 .. N), so that a wave loads neighbouring
+// entries: bit k of the result is set iff the entry exists, and x[k] is 0 where it does not.
+__device__ __forceinline__ uint32_t
+strided_of(const uint64_t *__restrict__ a, uint64_t N, uint64_t first, uint64_t (&x)[PER_THREAD])
+{
+	uint32_t valid = 0;
+#pragma unroll
+	for (uint32_t k = 0; k < PER_THREAD; k++) {
+		const uint64_t e = first + k * THREADS + threadIdx.x;
+		const bool has = e < N;
+		x[k] = has ? a[e] : 0;
+		valid |= (has ? 1u : 0u) << k;
+	}
+	return valid;
+}
+
+// A wave's ballot over bit k of such a thread's 16 is 64 consecutive entries' bits: where, of a
+// tile's 64 words of bits that begin at index `base`, wave w's of round k is.
+template <typename B>
+__device__ __forceinline__ B
+word_of(B base, uint32_t k, uint32_t w)
+{
+	return base + k * WAVES + w;
+}
+
+// One wave: the sum of own over the lanes up to and including this one.  A lane a word of a tile,
+// own its set bits: less own, the set bits of the words before it.
+__device__ __forceinline__ uint32_t
+lanes_through(uint32_t own, uint32_t lane)
+{
+	uint32_t inc = own;
+#pragma unroll
+	for (uint32_t d = 1; d < 64; d <<= 1) {
+		const uint32_t up = __shfl_up(inc, d);
+		if (lane >= d)
+			inc += up;
+	}
+	return inc;
+}
+
 // A segmented scan over the NW waves of a workgroup: the join of the runs of the threads before
 // this one, in thread order.  P is a run of list entries reduced; JOIN(a, b) is run a, then run b
 // (a segment that begins in b closes a), with `none` its identity; UP(p, d) is the p of the lane
@@ -161,6 +225,96 @@ run_of(uint32_t ntiles)
 	const uint32_t seglen = (ntiles + CARRY_THREADS - 1) / CARRY_THREADS;
 	const uint32_t t0 = min(threadIdx.x * seglen, ntiles);
 	return {t0, min(t0 + seglen, ntiles)};
+}
+
+// The carry kernel's exclusive scan of a count a tile, in[stride * t]: a thread sums its run of
+// tiles, the threads scan that (wsum: CARRY_THREADS / 64 words of LDS), and it walks its run again
+// to leave in out[stride * t] the counts of the tiles before t.  Returns the sum over all tiles.
+// out may be in; out NULL: the sum alone.  Every thread of the workgroup calls it.
+template <typename T>
+__device__ __forceinline__ T
+tile_counts_scan(const T *in, T *out, size_t stride, uint32_t ntiles, T *wsum)
+{
+	const auto [t0, t1] = run_of(ntiles);
+	T mine = 0, all;
+	for (uint32_t t = t0; t < t1; t++)
+		mine += in[stride * t];
+	T cur = block_scan<CARRY_THREADS / 64>(mine, wsum, all);
+	if (out != nullptr) {
+		for (uint32_t t = t0; t < t1; t++) {
+			const T own = in[stride * t];
+			out[stride * t] = cur;
+			cur += own;
+		}
+	}
+	return all;
+}
+
+// The sum, minimum, maximum and OR of some values: what reduce.hip keeps per run, four consecutive
+// words of a scratch row.  (rollup.hip writes the four out: see its part.)
+struct stats {
+	uint64_t sum, mn, mx, bits;
+};
+
+constexpr stats NO_STATS = {0, ~0ull, 0, 0}; // of no value
+
+__device__ __forceinline__ void
+add(stats &a, const stats &b)
+{
+	a.sum += b.sum;
+	a.mn = b.mn < a.mn ? b.mn : a.mn;
+	a.mx = b.mx > a.mx ? b.mx : a.mx;
+	a.bits |= b.bits;
+}
+
+__device__ __forceinline__ void
+add_value(stats &a, uint64_t v)
+{
+	a.sum += v;
+	a.mn = v < a.mn ? v : a.mn;
+	a.mx = v > a.mx ? v : a.mx;
+	a.bits |= v;
+}
+
+// the stats of the lane d below
+__device__ __forceinline__ stats
+up(const stats &s, uint32_t d)
+{
+	return {__shfl_up((unsigned long long)s.sum, d), __shfl_up((unsigned long long)s.mn, d),
+		__shfl_up((unsigned long long)s.mx, d), __shfl_up((unsigned long long)s.bits, d)};
+}
+
+__device__ __forceinline__ void
+store(uint64_t *__restrict__ w, const stats &s)
+{
+	w[0] = s.sum;
+	w[1] = s.mn;
+	w[2] = s.mx;
+	w[3] = s.bits;
+}
+
+__device__ __forceinline__ stats
+load(const uint64_t *__restrict__ w)
+{
+	return {w[0], w[1], w[2], w[3]};
+}
+
+// One statistic on its own (a file's further outputs are numbered from STATS on; one that is
+// none of MIN, MAX and BITS folds as a sum).
+enum { SUM, MIN, MAX, BITS, STATS };
+
+template <int STAT>
+__device__ __forceinline__ uint64_t
+ident()
+{
+	return STAT == MIN ? ~0ull : 0;
+}
+
+template <int STAT>
+__device__ __forceinline__ uint64_t
+fold(uint64_t a, uint64_t b)
+{
+	return STAT == MIN ? (b < a ? b : a) : STAT == MAX ? (b > a ? b : a) : STAT == BITS ? a | b : a + b;
 }
 
 // Run-time booleans as template flags: f(std::bool_constant<b>{}, std::bool_constant<rest>{}...),

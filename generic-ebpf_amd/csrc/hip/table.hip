@@ -62,30 +62,14 @@ struct merge_args {
 	uint64_t keep_lo, keep_hi;
 };
 
-// the valid entries of a table: a short one is its first cap entries
-__device__ __forceinline__ uint64_t
-entries_of(const table &t)
+// the valid entries of a table (one without n has cap 0, table.cpp table_null: no entry)
+__device__ __forceinline__ seq
+seq_of(const table &t)
 {
 	if (t.n == nullptr)
-		return 0;
+		return {t.keys, 0};
 	const uint64_t n = *t.n;
-	return n < t.cap ? n : t.cap;
-}
-
-// A thread's entries first + k * THREADS + tid of s: bit k of the result is set iff the entry
-// exists, and key[k] is 0 where it does not.
-__device__ __forceinline__ uint32_t
-keys_of(const seq &s, uint64_t first, uint64_t (&key)[PER_THREAD])
-{
-	uint32_t valid = 0;
-#pragma unroll
-	for (uint32_t k = 0; k < PER_THREAD; k++) {
-		const uint64_t e = first + k * THREADS + threadIdx.x;
-		const bool has = e < s.n;
-		key[k] = has ? s.keys[e] : 0;
-		valid |= (has ? 1u : 0u) << k;
-	}
-	return valid;
+	return {t.keys, n < t.cap ? n : t.cap};
 }
 
 // Where the tile's keys can stand in s: [lo, hi], the lower bounds of the smallest and of the
@@ -202,13 +186,13 @@ table_lookup(table t, const uint64_t *__restrict__ keys, uint64_t key_cap,
 	     uint64_t *__restrict__ vals_out, uint32_t *__restrict__ pos_out)
 {
 	__shared__ search_lds l;
-	const seq tab = {t.keys, entries_of(t)}, batch = {keys, segments_of(key_cap, nkeys)};
+	const seq tab = seq_of(t), batch = {keys, segments_of(key_cap, nkeys)};
 	const uint64_t first = (uint64_t)blockIdx.x * TILE;
 	if (first >= batch.n)
 		return;
 	uint64_t key[PER_THREAD], v[PER_THREAD];
 	uint32_t at[PER_THREAD], lo, hi;
-	const uint32_t valid = keys_of(batch, first, key);
+	const uint32_t valid = strided_of(batch.keys, batch.n, first, key);
 	range_of(tab, key, valid, l, lo, hi);
 	lower_bounds(tab.keys, lo, hi, key, at);
 	const uint32_t there = partners_of(tab, key, at, valid);
@@ -241,7 +225,7 @@ candidates(const merge_args &a, const seq &tab, const seq &batch, uint64_t first
 {
 	const seq &self = BATCH ? batch : tab, &other = BATCH ? tab : batch;
 	uint32_t lo, hi;
-	const uint32_t valid = keys_of(self, first, key);
+	const uint32_t valid = strided_of(self.keys, self.n, first, key);
 	range_of(other, key, valid, l, lo, hi);
 	lower_bounds(other.keys, lo, hi, key, at);
 	const uint32_t match = partners_of(other, key, at, valid);
@@ -288,7 +272,7 @@ table_tiles(merge_args a, uint32_t tab_tiles, uint32_t ntiles, uint32_t *__restr
 	__shared__ search_lds l;
 	__shared__ uint32_t wpop[WORDS], wonly[WAVES];
 	const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6, t = blockIdx.x;
-	const seq tab = {a.in.keys, entries_of(a.in)}, batch = {a.keys, segments_of(a.key_cap, a.nkeys)};
+	const seq tab = seq_of(a.in), batch = {a.keys, segments_of(a.key_cap, a.nkeys)};
 	const bool side = t >= tab_tiles; // (the same for every thread, as is whether the tile has an entry)
 	const uint64_t first = (uint64_t)(side ? t - tab_tiles : t) * TILE;
 	const scratch_map m = map_of(scratch, ntiles);
@@ -307,8 +291,8 @@ table_tiles(merge_args a, uint32_t tab_tiles, uint32_t ntiles, uint32_t *__restr
 		const uint64_t word = __ballot(keep >> k & 1);
 		lone += __popcll(__ballot(only >> k & 1));
 		if (lane == 0) {
-			m.bits[(size_t)t * WORDS + k * WAVES + w] = word;
-			wpop[k * WAVES + w] = __popcll(word);
+			m.bits[word_of((size_t)t * WORDS, k, w)] = word;
+			wpop[word_of(0u, k, w)] = __popcll(word);
 		}
 	}
 	if (lane == 0)
@@ -316,14 +300,7 @@ table_tiles(merge_args a, uint32_t tab_tiles, uint32_t ntiles, uint32_t *__restr
 	__syncthreads();
 	if (w != 0)
 		return;
-	const uint32_t own = wpop[lane];
-	uint32_t inc = own;
-#pragma unroll
-	for (uint32_t d = 1; d < 64; d <<= 1) {
-		const uint32_t up = __shfl_up(inc, d);
-		if (lane >= d)
-			inc += up;
-	}
+	const uint32_t own = wpop[lane], inc = lanes_through(own, lane);
 	m.before[(size_t)t * WORDS + lane] = (uint16_t)(inc - own);
 	if (lane == 63) {
 		uint32_t all = 0;
@@ -335,44 +312,29 @@ table_tiles(merge_args a, uint32_t tab_tiles, uint32_t ntiles, uint32_t *__restr
 	}
 }
 
-// One workgroup: per side a thread walks its run of tiles (run_of) twice, first for its run's
-// total, then, with the totals of the threads before it, to leave in every tile's word the kept
-// entries of its side's tiles before.  A side's sum is at most its cap < 2^32: 32-bit sums.
+// One workgroup: per side tile_counts_scan leaves in every tile's word the kept entries of its
+// side's tiles before.  A side's sum is at most its cap < 2^32: 32-bit sums.
 __global__ void __launch_bounds__(CARRY_THREADS)
 table_carry(table in, table out, uint32_t tab_tiles, uint32_t ntiles,
 	    uint32_t *__restrict__ scratch, uint64_t *__restrict__ info)
 {
 	__shared__ uint32_t wsum[CARRY_THREADS / 64];
 	const scratch_map m = map_of(scratch, ntiles);
-	uint32_t K[2], fresh;
+	uint32_t K[2];
 	for (uint32_t side = 0; side < 2; side++) {
 		uint32_t *counts = m.counts + (side ? 2 * (size_t)tab_tiles : 0);
-		const auto [t0, t1] = run_of(side ? ntiles - tab_tiles : tab_tiles);
-		uint32_t mine = 0;
-		for (uint32_t t = t0; t < t1; t++)
-			mine += counts[2 * (size_t)t];
-		uint32_t cur = block_scan<CARRY_THREADS / 64>(mine, wsum, K[side]);
-		for (uint32_t t = t0; t < t1; t++) {
-			const uint32_t own = counts[2 * (size_t)t];
-			counts[2 * (size_t)t] = cur;
-			cur += own;
-		}
+		K[side] = tile_counts_scan(counts, counts, 2, side ? ntiles - tab_tiles : tab_tiles, wsum);
 	}
-	{ // the batch's keys that the table has not
-		const uint32_t *counts = m.counts + 2 * (size_t)tab_tiles;
-		const auto [t0, t1] = run_of(ntiles - tab_tiles);
-		uint32_t mine = 0;
-		for (uint32_t t = t0; t < t1; t++)
-			mine += counts[2 * (size_t)t + 1];
-		block_scan<CARRY_THREADS / 64>(mine, wsum, fresh);
-	}
+	// the batch's keys that the table has not
+	const uint32_t fresh = tile_counts_scan<uint32_t>(m.counts + 2 * (size_t)tab_tiles + 1, nullptr, 2,
+							  ntiles - tab_tiles, wsum);
 	if (threadIdx.x == 0) {
 		const uint64_t M = (uint64_t)K[0] + K[1];
 		m.head[0] = K[0];
 		m.head[1] = K[1];
 		info[0] = M;
 		info[1] = K[1];
-		info[2] = entries_of(in) + fresh - M;
+		info[2] = seq_of(in).n + fresh - M;
 		if (out.n != nullptr)
 			*out.n = M;
 	}
@@ -384,7 +346,7 @@ table_place(merge_args a, table out, uint32_t tab_tiles, uint32_t ntiles,
 {
 	__shared__ search_lds l;
 	const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6, t = blockIdx.x;
-	const seq tab = {a.in.keys, entries_of(a.in)}, batch = {a.keys, segments_of(a.key_cap, a.nkeys)};
+	const seq tab = seq_of(a.in), batch = {a.keys, segments_of(a.key_cap, a.nkeys)};
 	const bool side = t >= tab_tiles;
 	const uint64_t first = (uint64_t)(side ? t - tab_tiles : t) * TILE;
 	if (first >= (side ? batch.n : tab.n)) // (the same for every thread)
@@ -406,7 +368,7 @@ table_place(merge_args a, table out, uint32_t tab_tiles, uint32_t ntiles,
 		const uint64_t word = __ballot(keep >> k & 1);
 		if (!(keep >> k & 1))
 			continue;
-		uint64_t dest = base + m.before[(size_t)t * WORDS + k * WAVES + w] +
+		uint64_t dest = base + m.before[word_of((size_t)t * WORDS, k, w)] +
 				__popcll(word & ((1ull << lane) - 1));
 		// at[k] <= n_other: a position of the other side, or its end
 		const uint32_t j = at[k];
@@ -422,13 +384,6 @@ table_place(merge_args a, table out, uint32_t tab_tiles, uint32_t ntiles,
 			out.vals[dest] = val[k];
 		}
 	}
-}
-
-uint32_t
-tiles_of(uint64_t n)
-{
-	const uint64_t t = (n + TILE - 1) / TILE;
-	return t != 0 ? (uint32_t)t : 1;
 }
 
 } // namespace

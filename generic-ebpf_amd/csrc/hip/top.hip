@@ -66,37 +66,18 @@ map_of(uint32_t *scratch, uint32_t nrows)
 	return {scratch, reinterpret_cast<uint64_t *>(g), pos, rows, rows + (size_t)nrows * BINS};
 }
 
-// N, the entries that take part: the table's rule, or the reduce's
-__device__ __forceinline__ uint64_t
-entries_of(const top_args &a)
-{
-	if (a.segments)
-		return segments_of(a.cap, a.n);
-	if (a.n == nullptr)
-		return a.cap;
-	const uint64_t n = *a.n;
-	return n < a.cap ? n : a.cap;
-}
-
 __device__ __forceinline__ uint64_t
 prefix_of(const uint32_t *head)
 {
 	return *reinterpret_cast<const uint64_t *>(head);
 }
 
-// A thread's entries first + k * THREADS + tid in the order's terms: bit k of the result is set
-// iff the entry exists, and g[k] is 0 where it does not.
+// A thread's entries first + k * THREADS + tid of the N (strided_of) in the order's terms: g[k] is
+// 0 where the entry does not exist.
 __device__ __forceinline__ uint32_t
 load_tile(const top_args &a, uint64_t N, uint64_t first, uint64_t (&g)[PER_THREAD])
 {
-	uint32_t valid = 0;
-#pragma unroll
-	for (uint32_t k = 0; k < PER_THREAD; k++) {
-		const uint64_t e = first + k * THREADS + threadIdx.x;
-		const bool has = e < N;
-		g[k] = has ? a.vals[e] : 0;
-		valid |= (has ? 1u : 0u) << k;
-	}
+	const uint32_t valid = strided_of(a.vals, N, first, g);
 #pragma unroll
 	for (uint32_t k = 0; k < PER_THREAD; k++) {
 		const uint64_t v = a.f.of(g[k]);
@@ -131,7 +112,7 @@ top_count(top_args a, uint32_t shift, uint32_t first_pass, uint32_t per_row, uin
 	__shared__ uint32_t hist[BINS];
 	const scratch_map m = map_of(scratch, nrows);
 	const uint32_t lane = threadIdx.x & 63, row = blockIdx.x;
-	const uint64_t N = entries_of(a);
+	const uint64_t N = entries_of(a.cap, a.n, a.segments);
 	const uint64_t prefix = first_pass ? 0 : prefix_of(m.head);
 	const uint32_t hi = shift + 8; // (the bits from here up are the prefix's; 64: there are none)
 	hist[threadIdx.x] = 0;
@@ -196,7 +177,7 @@ top_pick(top_args a, uint64_t k, uint32_t shift, uint32_t first_pass, uint32_t n
 	uint64_t prefix = 0;
 	uint32_t want;
 	if (first_pass) {
-		const uint64_t N = entries_of(a);
+		const uint64_t N = entries_of(a.cap, a.n, a.segments);
 		want = (uint32_t)(k < N ? k : N); // m: k <= EBPF_TOP_MAX
 		if (lane == 0)
 			m.head[3] = want;
@@ -212,13 +193,7 @@ top_pick(top_args a, uint64_t k, uint32_t shift, uint32_t first_pass, uint32_t n
 		c[i] = total[bin];
 		own += c[i];
 	}
-	uint32_t inc = own;
-#pragma unroll
-	for (uint32_t d = 1; d < 64; d <<= 1) {
-		const uint32_t up = __shfl_up(inc, d);
-		if (lane >= d)
-			inc += up;
-	}
+	const uint32_t inc = lanes_through(own, lane);
 	// the lane whose bins hold the want-th entry from the top (none for want == 0)
 	uint32_t before = inc - own, digit = 0;
 	const bool here = want != 0 && before < want && want <= inc;
@@ -276,7 +251,7 @@ top_tiles(top_args a, uint32_t nrows, uint32_t *__restrict__ scratch)
 	__shared__ uint32_t wsum[WAVES][2];
 	const scratch_map m = map_of(scratch, nrows);
 	const uint32_t t = blockIdx.x;
-	const uint64_t N = entries_of(a), first = (uint64_t)t * TILE;
+	const uint64_t N = entries_of(a.cap, a.n, a.segments), first = (uint64_t)t * TILE;
 	uint32_t above = 0, equal = 0, na, ne;
 	if (first < N) { // (the same for every thread)
 		uint64_t g[PER_THREAD];
@@ -290,25 +265,16 @@ top_tiles(top_args a, uint32_t nrows, uint32_t *__restrict__ scratch)
 	}
 }
 
-// One workgroup: per kind a thread walks its run of tiles (run_of) twice, first for its run's
-// total, then, with the totals of the threads before it, to leave beside every tile's count the
-// entries of that kind in the tiles before.  A sum is at most cap < 2^32.
+// One workgroup: per kind tile_counts_scan leaves beside every tile's count the entries of that
+// kind in the tiles before.  A sum is at most cap < 2^32.
 __global__ void __launch_bounds__(CARRY_THREADS)
 top_carry(uint32_t ntiles, uint32_t nrows, uint32_t *__restrict__ scratch)
 {
 	__shared__ uint32_t wsum[CARRY_THREADS / 64];
 	const scratch_map m = map_of(scratch, nrows);
-	const auto [t0, t1] = run_of(ntiles);
 	for (uint32_t kind = 0; kind < 2; kind++) {
 		uint32_t *counts = m.counts + kind;
-		uint32_t mine = 0, all;
-		for (uint32_t t = t0; t < t1; t++)
-			mine += counts[TOP_TILE_WORDS * (size_t)t];
-		uint32_t cur = block_scan<CARRY_THREADS / 64>(mine, wsum, all);
-		for (uint32_t t = t0; t < t1; t++) {
-			counts[TOP_TILE_WORDS * (size_t)t + 2] = cur;
-			cur += counts[TOP_TILE_WORDS * (size_t)t];
-		}
+		const uint32_t all = tile_counts_scan(counts, counts + 2, TOP_TILE_WORDS, ntiles, wsum);
 		if (threadIdx.x == 0)
 			m.head[4 + kind] = all;
 	}
@@ -327,7 +293,7 @@ top_place(top_args a, uint32_t nrows, uint32_t *__restrict__ scratch)
 	// nothing above the cut and no equal entry of rank below e
 	if (mine[0] == 0 && (mine[1] == 0 || base_e >= e))
 		return;
-	const uint64_t N = entries_of(a), first = (uint64_t)t * TILE;
+	const uint64_t N = entries_of(a.cap, a.n, a.segments), first = (uint64_t)t * TILE;
 	if (first >= N)
 		return;
 	uint64_t g[PER_THREAD];
@@ -338,20 +304,13 @@ top_place(top_args a, uint32_t nrows, uint32_t *__restrict__ scratch)
 	for (uint32_t k = 0; k < PER_THREAD; k++) {
 		const uint64_t wa = __ballot(above >> k & 1), we = __ballot(equal >> k & 1);
 		if (lane == 0) {
-			wpop[0][k * WAVES + w] = __popcll(wa);
-			wpop[1][k * WAVES + w] = __popcll(we);
+			wpop[0][word_of(0u, k, w)] = __popcll(wa);
+			wpop[1][word_of(0u, k, w)] = __popcll(we);
 		}
 	}
 	__syncthreads();
 	if (w < 2) { // the set bits of the tile's words before each, of either kind
-		const uint32_t own = wpop[w][lane];
-		uint32_t inc = own;
-#pragma unroll
-		for (uint32_t d = 1; d < 64; d <<= 1) {
-			const uint32_t up = __shfl_up(inc, d);
-			if (lane >= d)
-				inc += up;
-		}
+		const uint32_t own = wpop[w][lane], inc = lanes_through(own, lane);
 		wpop[w][lane] = inc - own;
 	}
 	__syncthreads();
@@ -362,9 +321,9 @@ top_place(top_args a, uint32_t nrows, uint32_t *__restrict__ scratch)
 		const uint64_t lower = (1ull << lane) - 1;
 		uint32_t dest = NO_POS;
 		if (above >> k & 1) {
-			dest = base_a + wpop[0][k * WAVES + w] + __popcll(wa & lower);
+			dest = base_a + wpop[0][word_of(0u, k, w)] + __popcll(wa & lower);
 		} else if (equal >> k & 1) {
-			const uint32_t r = base_e + wpop[1][k * WAVES + w] + __popcll(we & lower);
+			const uint32_t r = base_e + wpop[1][word_of(0u, k, w)] + __popcll(we & lower);
 			dest = r < e ? (taken - e) + r : NO_POS;
 		}
 		if (dest < slots) {
@@ -389,7 +348,7 @@ top_order(top_args a, uint32_t nrows, uint32_t *__restrict__ scratch, tops out,
 	__shared__ uint64_t sg[EBPF_TOP_MAX];
 	__shared__ uint32_t sp[EBPF_TOP_MAX];
 	const scratch_map m = map_of(scratch, nrows);
-	const uint64_t N = entries_of(a);
+	const uint64_t N = entries_of(a.cap, a.n, a.segments);
 	const uint32_t taken = m.head[3] < EBPF_TOP_MAX ? m.head[3] : EBPF_TOP_MAX;
 	uint32_t P = 1; // the network's size: a power of two, at least taken
 	while (P < taken)
@@ -433,13 +392,6 @@ top_order(top_args a, uint32_t nrows, uint32_t *__restrict__ scratch, tops out,
 		info[2] = taken == 0 ? 0 : (a.smallest ? a.f.mask - T : T);
 		info[3] = taken == 0 ? 0 : m.head[5] - m.head[2];
 	}
-}
-
-uint32_t
-tiles_of(uint64_t n)
-{
-	const uint64_t t = (n + TILE - 1) / TILE;
-	return t != 0 ? (uint32_t)t : 1;
 }
 
 // the tiles of a row, and the rows

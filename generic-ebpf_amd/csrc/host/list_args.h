@@ -1,7 +1,8 @@
 // list_args.h — the argument rules that the list operations share on the host (reduce.cpp,
-// scan.cpp, filter.cpp; group.cpp for its key): a bit field of ret, the 32-bit sizes, a batch and a
-// list, and a list's segment table (ebpf_gpu.h).  The device states the segment count once more:
-// seg_tile.h segments_of.
+// scan.cpp, filter.cpp; group.cpp for its key; table.cpp, top.cpp and rollup.cpp for their
+// entries): a bit field of ret, the 32-bit sizes, a batch and a list, a list's segment table and a
+// keyed sequence's entries (ebpf_gpu.h).  The device states the two counts once more: seg_tile.h
+// segments_of and entries_of.
 #pragma once
 #include <string>
 
@@ -52,6 +53,14 @@ inline uint64_t
 seg_count(const uint64_t *nseg, uint64_t seg_cap)
 {
 	return nseg == nullptr ? seg_cap : *nseg <= seg_cap ? *nseg : (seg_cap != 0 ? seg_cap - 1 : 0);
+}
+
+// The entries of a keyed sequence that take part: the rule above, or the table's, a short sequence
+// (*n > cap) being its first cap entries.  (The device's statement: seg_tile.h entries_of.)
+inline uint64_t
+entry_count(const uint64_t *n, uint64_t cap, bool segments)
+{
+	return segments ? seg_count(n, cap) : n == nullptr ? cap : (*n < cap ? *n : cap);
 }
 
 inline int

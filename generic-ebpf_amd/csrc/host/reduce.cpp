@@ -7,12 +7,6 @@
 
 namespace {
 
-inline bool
-wants_values(const struct ebpf_batch_sums &o)
-{
-	return o.sum != nullptr || o.min != nullptr || o.max != nullptr || o.bits != nullptr;
-}
-
 int
 reduce_args(const struct ebpf_pkt_batch *batch, const uint64_t *ret, uint64_t count,
 	    uint32_t val_shift, uint32_t val_bits, const uint32_t *index, uint64_t n,

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "ebpf_gpu.h"
+#include "host/wants_values.h"
 
 // A scratch row, in u64 words: bytes, sum, min, max, bits, and one word about the tile.
 constexpr uint32_t REDUCE_ROW_WORDS = 6;

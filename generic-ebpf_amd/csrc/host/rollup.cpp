@@ -6,13 +6,6 @@
 
 namespace {
 
-// does an output read the values?
-bool
-uses_vals(const struct ebpf_batch_rolls &out)
-{
-	return out.sum != nullptr || out.min != nullptr || out.max != nullptr || out.bits != nullptr;
-}
-
 int
 rollup_args(const uint64_t *keys, const uint64_t *vals, uint64_t cap, uint32_t flags,
 	    uint32_t key_shift, uint32_t val_shift, uint32_t val_bits, uint64_t out_cap,
@@ -24,25 +17,16 @@ rollup_args(const uint64_t *keys, const uint64_t *vals, uint64_t cap, uint32_t f
 		return fail(EINVAL, "unknown flags");
 	if (key_shift > 63)
 		return fail(EINVAL, "key_shift above 63");
-	if (uses_vals(*out))
+	if (wants_values(*out))
 		if (int err = check_field(val_shift, val_bits))
 			return err;
 	if (cap != 0 && keys == nullptr)
 		return fail(EINVAL, "keys is NULL with cap > 0");
-	if (cap != 0 && vals == nullptr && uses_vals(*out))
+	if (cap != 0 && vals == nullptr && wants_values(*out))
 		return fail(EINVAL, "vals is NULL with cap > 0 and an output of the values wanted");
 	if (cap > 0xffffffffull || out_cap > 0xffffffffull)
 		return fail(E2BIG, "cap or out_cap above 2^32 - 1");
 	return 0;
-}
-
-// The entries that take part: the table's rule, or the reduce's.
-uint64_t
-entries(const uint64_t *n, uint64_t cap, uint32_t flags)
-{
-	if (flags & EBPF_ROLLUP_SEGMENTS)
-		return seg_count(n, cap);
-	return n == nullptr ? cap : (*n < cap ? *n : cap);
 }
 
 } // namespace
@@ -56,8 +40,8 @@ ebpf_batch_rollup(const uint64_t *keys, const uint64_t *vals, uint64_t cap, cons
 	if (int err = rollup_args(keys, vals, cap, flags, key_shift, val_shift, val_bits, out_cap, out,
 				  info))
 		return err;
-	const uint64_t N = entries(n, cap, flags);
-	const bool values = uses_vals(*out);
+	const uint64_t N = entry_count(n, cap, flags & EBPF_ROLLUP_SEGMENTS);
+	const bool values = wants_values(*out);
 	const bit_field f = values ? field_of(val_shift, val_bits) : field_of(0, 64);
 	uint64_t C = 0;
 	for (uint64_t a = 0, b; a < N; a = b, C++) {

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "ebpf_gpu.h"
+#include "host/wants_values.h"
 
 // The tiles of one call: those of the cap entries, STEER_TILE each; a sequence of no entry still
 // has one.  Library scratch of one call, any contents on entry: a row of ROLLUP_ROW_WORDS u64 a

@@ -52,11 +52,11 @@ accumulate_args(const struct ebpf_key_table *in, const uint64_t *keys, const uin
 	return 0;
 }
 
-// The valid entries of a table: a short one is its first cap entries.
+// The valid entries of a table (one without n has cap 0, by table_null: no entry).
 uint64_t
 entries(const struct ebpf_key_table &t)
 {
-	return t.n == nullptr ? 0 : (*t.n < t.cap ? *t.n : t.cap);
+	return entry_count(t.n, t.cap, false);
 }
 
 int

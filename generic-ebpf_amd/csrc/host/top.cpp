@@ -28,15 +28,6 @@ top_args(const uint64_t *keys, const uint64_t *vals, uint64_t cap, uint32_t flag
 	return 0;
 }
 
-// The entries that take part: the table's rule, or the reduce's.
-uint64_t
-entries(const uint64_t *n, uint64_t cap, uint32_t flags)
-{
-	if (flags & EBPF_TOP_SEGMENTS)
-		return seg_count(n, cap);
-	return n == nullptr ? cap : (*n < cap ? *n : cap);
-}
-
 } // namespace
 
 // A partial sort over positions: the reference for the device kernels.
@@ -47,7 +38,7 @@ ebpf_batch_top(const uint64_t *keys, const uint64_t *vals, uint64_t cap, const u
 {
 	if (int err = top_args(keys, vals, cap, flags, val_shift, val_bits, k, out, info))
 		return err;
-	const uint64_t N = entries(n, cap, flags), m = k < N ? k : N;
+	const uint64_t N = entry_count(n, cap, flags & EBPF_TOP_SEGMENTS), m = k < N ? k : N;
 	const bit_field f = field_of(val_shift, val_bits);
 	const bool smallest = flags & EBPF_TOP_SMALLEST;
 	std::vector<uint32_t> p(N);

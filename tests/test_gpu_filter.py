@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import pyoracle
+from gpu_buffers import run, up
 from test_reduce import BIG, COUNTS, GUARD, MID, SEGMENTATIONS, T, U64, list_of
 from test_filter import (FILL, KINDS, NO_PACKET, PARTS, TYPES, WANTS, Case, host, shaped, vector)
 
@@ -25,20 +26,9 @@ pytestmark = pytest.mark.gpu
 
 OTHER = {"kept": 0x01234567, "kept_starts": 0x0123456789abcdef, "dropped": 0x01234567,
          "dropped_starts": 0x0123456789abcdef, "info": 0x0123456789abcdef}
-SIGNED = {np.uint32: np.int32, U64: np.int64, np.uint8: np.uint8}
 # the patterns that stress the compaction: all, none, one per tile at its last position, one per
 # wave, half and one in a hundred at random
 PATTERNS = ["flags_all", "flags_none", "flags_tile_last", "flags_wave", "flags_half", "flags_1pct"]
-
-
-def _up(a, dtype, skew=0):
-    """a on the device; skew: that many bytes past a 256-byte boundary"""
-    import torch
-    a = np.ascontiguousarray(a).view(np.uint8)
-    buf = torch.zeros(len(a) + 256, dtype=torch.uint8, device="cuda:0")
-    assert buf.data_ptr() % 256 == 0
-    buf[skew:skew + len(a)] = torch.from_numpy(a)
-    return buf[skew:skew + len(a)]
 
 
 class Dev:
@@ -47,15 +37,14 @@ class Dev:
 
     def __init__(self, c, fill=FILL, skew=False):
         self.c, self.fill = c, fill
-        self.index = _up(c.index, np.int32)
-        self.starts = None if c.seg_starts is None else _up(c.seg_starts, np.int64)
-        self.nseg = None if c.nseg is None else _up(np.array([c.nseg], dtype=U64), np.int64)
-        self.flags = None if c.flags is None else _up(c.flags, np.uint8, 1 if skew else 0)
-        self.rank = None if c.rank is None else _up(c.rank, np.int32, 4 if skew else 0)
+        self.index = up(c.index)
+        self.starts = None if c.seg_starts is None else up(c.seg_starts)
+        self.nseg = None if c.nseg is None else up(np.array([c.nseg], dtype=U64))
+        self.flags = None if c.flags is None else up(c.flags, 1 if skew else 0)
+        self.rank = None if c.rank is None else up(c.rank, 4 if skew else 0)
         # (a batch of no packets still names a ret where values are tested: one unused word)
-        self.ret = None if c.ret is None else _up(c.ret if len(c.ret) else np.zeros(1, U64),
-                                                  np.int64)
-        self.outs = {k: _up(np.full(c.size(k) + GUARD, fill[k], dtype=TYPES[k]), None,
+        self.ret = None if c.ret is None else up(c.ret if len(c.ret) else np.zeros(1, U64))
+        self.outs = {k: up(np.full(c.size(k) + GUARD, fill[k], dtype=TYPES[k]),
                             (TYPES[k]().itemsize if skew else 0))
                      for k in c.want + ("info",)}
 
@@ -82,13 +71,6 @@ class Dev:
         for k in w:
             np.testing.assert_array_equal(got[k], w[k], err_msg="%s: %s" % (msg, k))
         return got
-
-
-def run(gpu, devs):
-    import torch
-    for d in devs:
-        assert d.enqueue(gpu, torch.cuda.current_stream()) == 0
-    torch.cuda.synchronize()
 
 
 @pytest.mark.parametrize("n", sorted(set(COUNTS + [15, 16, 17])))
@@ -256,7 +238,7 @@ def test_filter_in_a_quota_pipeline_on_one_stream(gpu, env):
 
     def z(k, dtype, fill=0):
         return torch.full((k,), fill, dtype=dtype, device=dev)
-    d_data, d_offs = _up(data, np.uint8), _up(offsets, np.int64)
+    d_data, d_offs = up(data), up(offsets)
     ret, flt = z(NREAL, torch.int64, -1), z(NREAL, torch.uint8)
     index, gkeys, gstarts = z(NREAL, torch.int32, -1), z(cap, torch.int64), z(cap + 1, torch.int64)
     info, kd = z(2, torch.int64), z(2, torch.int64, 0x5a)

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import pyoracle
+from gpu_buffers import run, up
 from test_reduce import (BIG, COUNTS, GUARD, IDENTITY, MID, SEGMENTATIONS, SENTINEL, SUMS, T, U64,
                          Case, batch_form, list_of, reference, segmentation, shaped, verdicts)
 
@@ -24,11 +25,6 @@ FORMS = ["stride64", "stride60", "offsets", "extents"]
 WIDTHS = [1, 8, 32, 33, 64]
 
 
-def _up(a, dtype):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(dtype)).to(torch.device("cuda:0"))
-
-
 class Dev:
     """one reduce call's device buffers; outputs pre-filled with `fill`"""
 
@@ -36,13 +32,12 @@ class Dev:
         import torch
         dev = torch.device("cuda:0")
         self.c, self.fill = c, fill
-        self.index = _up(c.index, np.int32)
-        self.starts = _up(c.seg_starts, np.int64)
+        self.index = up(c.index)
+        self.starts = up(c.seg_starts)
         # (a batch of no packets still names a ret where values are wanted: one unused word)
-        self.ret = None if c.ret is None else _up(c.ret if len(c.ret) else np.zeros(1, U64),
-                                                  np.int64)
-        self.offsets = None if c.offsets is None else _up(c.offsets, np.int64)
-        self.nseg = None if c.nseg is None else _up(np.array([c.nseg], dtype=U64), np.int64)
+        self.ret = None if c.ret is None else up(c.ret if len(c.ret) else np.zeros(1, U64))
+        self.offsets = None if c.offsets is None else up(c.offsets)
+        self.nseg = None if c.nseg is None else up(np.array([c.nseg], dtype=U64))
         signed = int(np.array([fill], dtype=U64).view(np.int64)[0])
         self.outs = {k: torch.full((c.cap + GUARD,), signed, dtype=torch.int64, device=dev)
                      for k in c.want}
@@ -71,13 +66,6 @@ class Dev:
             np.testing.assert_array_equal(got[k][:R], w[k][:R], err_msg="%s: %s" % (msg, k))
             assert (got[k][R:] == U64(self.fill)).all(), "%s: %s written at or past R" % (msg, k)
         return got
-
-
-def run(gpu, devs):
-    import torch
-    for d in devs:
-        assert d.enqueue(gpu, torch.cuda.current_stream()) == 0
-    torch.cuda.synchronize()
 
 
 @pytest.mark.parametrize("n", COUNTS)
@@ -235,7 +223,7 @@ def test_reduce_after_group_on_one_stream(gpu, env):
         data, NREAL, 0, offsets=offsets)
     dev = torch.device("cuda:0")
     st = torch.cuda.current_stream().cuda_stream
-    d_data, d_offs = _up(data, np.uint8), _up(offsets, np.int64)
+    d_data, d_offs = up(data), up(offsets)
     ret = torch.full((NREAL,), -1, dtype=torch.int64, device=dev)
     flt = torch.zeros(NREAL, dtype=torch.uint8, device=dev)
     cap = NREAL
@@ -287,7 +275,7 @@ def test_reduce_after_steer_on_one_stream(gpu, env):
     lay = _program("ldxb", 20)
     dev = torch.device("cuda:0")
     st = torch.cuda.current_stream().cuda_stream
-    d_data, d_offs = _up(data, np.uint8), _up(offsets, np.int64)
+    d_data, d_offs = up(data), up(offsets)
     ret = torch.full((NREAL,), -1, dtype=torch.int64, device=dev)
     flt = torch.zeros(NREAL, dtype=torch.uint8, device=dev)
     index = torch.full((NREAL,), -1, dtype=torch.int32, device=dev)

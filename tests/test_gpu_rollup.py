@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from generic_ebpf_amd import native as _native
+from gpu_buffers import ptr, run, up
 from test_rollup import (ALL, FIELDS, FILL, GUARD, INFO_FILL, SEGMENTS, U64, Roll,
                          host_rollup, keys_of_runs, lengths_of, random_vals)
 
@@ -27,37 +28,23 @@ WANTS = [ALL, ("count",), ("keys", "count", "starts"), ("sum",), ("keys", "min",
 OTHER = 0x0123456789abcdef
 
 
-def _up(a, skew=0):
-    """a on the device; skew: that many bytes past a 256-byte boundary"""
-    import torch
-    a = np.ascontiguousarray(a).view(np.uint8)
-    buf = torch.zeros(len(a) + 256, dtype=torch.uint8, device="cuda:0")
-    assert buf.data_ptr() % 256 == 0
-    buf[skew:skew + len(a)] = torch.from_numpy(a)
-    return buf[skew:skew + len(a)]
-
-
-def _ptr(t):
-    return t.data_ptr() if t.numel() else None
-
-
 class DevRoll:
     """a Roll's arrays and outputs on the device"""
 
     def __init__(self, c, fill=FILL, skew=False):
         self.c, self.fill = c, fill
         s = 8 if skew else 0
-        self.keys = _up(c.keys, s)
-        self.vals = None if c.vals is None else _up(c.vals, s)
-        self.n = None if c.n is None else _up(np.array([c.n], dtype=U64), s)
-        self.outs = {w: _up(np.full(c.size(w), fill, dtype=U64), s) for w in c.want}
-        self.outs["info"] = _up(np.full(2 + GUARD, INFO_FILL, dtype=U64), s)
+        self.keys = up(c.keys, s)
+        self.vals = None if c.vals is None else up(c.vals, s)
+        self.n = None if c.n is None else up(np.array([c.n], dtype=U64), s)
+        self.outs = {w: up(np.full(c.size(w), fill, dtype=U64), s) for w in c.want}
+        self.outs["info"] = up(np.full(2 + GUARD, INFO_FILL, dtype=U64), s)
 
     def enqueue(self, gpu, stream):
         c = self.c
         rolls = gpu.BatchRolls(*[self.outs[w].data_ptr() if w in c.want else None for w in ALL])
         return gpu.lib().ebpf_batch_rollup_dev(
-            0, _ptr(self.keys), None if self.vals is None else _ptr(self.vals), c.cap,
+            0, ptr(self.keys), None if self.vals is None else ptr(self.vals), c.cap,
             None if self.n is None else self.n.data_ptr(), c.flags, c.shift, c.field[0], c.field[1],
             c.out_cap, ctypes.byref(rolls), self.outs["info"].data_ptr(), stream.cuda_stream)
 
@@ -70,13 +57,6 @@ class DevRoll:
         for k in w:
             np.testing.assert_array_equal(got[k], w[k], err_msg="%s: %s" % (msg, k))
         return got
-
-
-def run(gpu, devs):
-    import torch
-    for d in devs:
-        assert d.enqueue(gpu, torch.cuda.current_stream()) == 0
-    torch.cuda.synchronize()
 
 
 def check_all(gpu, devs):
@@ -304,7 +284,7 @@ def test_distinct_sources_per_destination_of_a_batch(gpu):
     offsets = np.concatenate([[0], np.cumsum(lens)]).astype(U64)
     cap, rcap = count, 64
     st = torch.cuda.current_stream().cuda_stream
-    d_ret, d_offs = _up(ret), _up(offsets)
+    d_ret, d_offs = up(ret), up(offsets)
     index = _z(count, -1, torch.int32)
     gkeys, gstarts, info = _z(cap, 0x5a), _z(cap + 1, 0x5a), _z(2)
     tmp_bytes = gpu.group_tmp_bytes(count, 64)
@@ -367,7 +347,7 @@ def test_a_carried_table_rolled_up(gpu):
     keep = []
     for b, (keys, adds) in enumerate(batches):
         cur, nxt = tables[b % 2], tables[1 - b % 2]
-        d_keys, d_adds, ainfo = _up(keys), _up(adds), _z(3)
+        d_keys, d_adds, ainfo = up(keys), up(adds), _z(3)
         gpu.accumulate_dev(0, None if b == 0 else (cur[0].data_ptr(), cur[1].data_ptr(), tcap,
                                                    cur[2].data_ptr()),
                            d_keys.data_ptr(), d_adds.data_ptr(), len(keys),

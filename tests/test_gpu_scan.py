@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import pyoracle
+from gpu_buffers import run, up
 from test_reduce import (BIG, COUNTS, GUARD, MID, SEGMENTATIONS, T, U64, Case, batch_form,
                          list_of, segmentation, verdicts)
 from test_scan import FILL, FORMS, SCANS, TYPES, budgets_of, host, places, shaped
@@ -25,12 +26,6 @@ pytestmark = pytest.mark.gpu
 WIDTHS = [1, 8, 32, 33, 64]
 OTHER = {"rank": 0x01234567, "bytes_before": 0x0123456789abcdef,
          "sum_before": 0x0123456789abcdef, "over": 0xa7}
-SIGNED = {np.uint32: np.int32, U64: np.int64, np.uint8: np.uint8}
-
-
-def _up(a, dtype):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(dtype)).to(torch.device("cuda:0"))
 
 
 class Dev:
@@ -41,16 +36,15 @@ class Dev:
         if budgets is None and "over" in c.want:
             budgets = budgets_of(c)
         self.host_budgets = budgets
-        self.index = _up(c.index, np.int32)
-        self.starts = _up(c.seg_starts, np.int64)
+        self.index = up(c.index)
+        self.starts = up(c.seg_starts)
         # (a batch of no packets still names a ret where values are wanted: one unused word)
-        self.ret = None if c.ret is None else _up(c.ret if len(c.ret) else np.zeros(1, U64),
-                                                  np.int64)
-        self.offsets = None if c.offsets is None else _up(c.offsets, np.int64)
-        self.nseg = None if c.nseg is None else _up(np.array([c.nseg], dtype=U64), np.int64)
-        self.budgets = None if budgets is None else _up(
-            budgets if len(budgets) else np.zeros(1, U64), np.int64)
-        self.outs = {k: _up(np.full(c.n + GUARD, fill[k], dtype=TYPES[k]), SIGNED[TYPES[k]])
+        self.ret = None if c.ret is None else up(c.ret if len(c.ret) else np.zeros(1, U64))
+        self.offsets = None if c.offsets is None else up(c.offsets)
+        self.nseg = None if c.nseg is None else up(np.array([c.nseg], dtype=U64))
+        self.budgets = None if budgets is None else up(
+            budgets if len(budgets) else np.zeros(1, U64))
+        self.outs = {k: up(np.full(c.n + GUARD, fill[k], dtype=TYPES[k]))
                      for k in c.want}
 
     def enqueue(self, gpu, stream):
@@ -77,13 +71,6 @@ class Dev:
         for k in self.c.want:
             np.testing.assert_array_equal(got[k], w[k], err_msg="%s: %s" % (msg, k))
         return got
-
-
-def run(gpu, devs):
-    import torch
-    for d in devs:
-        assert d.enqueue(gpu, torch.cuda.current_stream()) == 0
-    torch.cuda.synchronize()
 
 
 @pytest.mark.parametrize("n", COUNTS)
@@ -271,7 +258,7 @@ def test_scan_after_group_on_one_stream(gpu, env):
         data, NREAL, 0, offsets=offsets)
     dev = torch.device("cuda:0")
     st = torch.cuda.current_stream().cuda_stream
-    d_data, d_offs = _up(data, np.uint8), _up(offsets, np.int64)
+    d_data, d_offs = up(data), up(offsets)
     ret = torch.full((NREAL,), -1, dtype=torch.int64, device=dev)
     flt = torch.zeros(NREAL, dtype=torch.uint8, device=dev)
     cap = NREAL
@@ -282,7 +269,7 @@ def test_scan_after_group_on_one_stream(gpu, env):
     tmp_bytes = gpu.group_tmp_bytes(NREAL, 16)
     tmp = torch.zeros(max(tmp_bytes, 8), dtype=torch.uint8, device=dev)
     budgets = torch.full((cap,), BUDGET, dtype=torch.int64, device=dev)
-    outs = {k: _up(np.full(NREAL + GUARD, FILL[k], dtype=TYPES[k]), SIGNED[TYPES[k]])
+    outs = {k: up(np.full(NREAL + GUARD, FILL[k], dtype=TYPES[k]))
             for k in SCANS}
     p = gpu.Prog(env, gpu.patch_relocs(lay.code, lay.relocs, []))
     try:

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from generic_ebpf_amd import native as _native
+from gpu_buffers import ptr, run, up
 from test_table import (FILL, GUARD, MAXU, PATTERNS, TYPES, U64, Acc, Look, Table, host_accumulate,
                         host_lookup, pattern)
 
@@ -30,46 +31,32 @@ OTHER = {"vals": 0x0123456789abcdef, "pos": 0x01234567, "keys": 0x0123456789abcd
          "n": 0x0123456789abcdef, "info": 0x0123456789abcdef}
 
 
-def _up(a, skew=0):
-    """a on the device; skew: that many bytes past a 256-byte boundary"""
-    import torch
-    a = np.ascontiguousarray(a).view(np.uint8)
-    buf = torch.zeros(len(a) + 256, dtype=torch.uint8, device="cuda:0")
-    assert buf.data_ptr() % 256 == 0
-    buf[skew:skew + len(a)] = torch.from_numpy(a)
-    return buf[skew:skew + len(a)]
-
-
-def _ptr(t):
-    return t.data_ptr() if t.numel() else None
-
-
 class DevTable:
     """a Table's arrays on the device"""
 
     def __init__(self, t, skew=0):
         self.cap = t.cap
-        self.keys, self.vals = _up(t.keys, skew), _up(t.vals, skew)
-        self.n = _up(np.array([t.n], dtype=U64), skew)
+        self.keys, self.vals = up(t.keys, skew), up(t.vals, skew)
+        self.n = up(np.array([t.n], dtype=U64), skew)
 
     def struct(self, gpu):
-        return gpu.KeyTable(_ptr(self.keys), _ptr(self.vals), self.cap, self.n.data_ptr())
+        return gpu.KeyTable(ptr(self.keys), ptr(self.vals), self.cap, self.n.data_ptr())
 
 
 class DevLook:
     def __init__(self, c, fill=FILL, skew=False):
         self.c, self.fill = c, fill
         self.table = DevTable(c.table, 8 if skew else 0)
-        self.keys = _up(c.keys, 8 if skew else 0)
-        self.nkeys = None if c.nkeys is None else _up(np.array([c.nkeys], dtype=U64))
-        self.outs = {k: _up(np.full(c.cap + GUARD, fill[k], dtype=TYPES[k]),
+        self.keys = up(c.keys, 8 if skew else 0)
+        self.nkeys = None if c.nkeys is None else up(np.array([c.nkeys], dtype=U64))
+        self.outs = {k: up(np.full(c.cap + GUARD, fill[k], dtype=TYPES[k]),
                             (8 if k == "vals" else 4) if skew else 0) for k in c.want}
 
     def enqueue(self, gpu, stream):
         c = self.c
         t = self.table.struct(gpu)
         return gpu.lib().ebpf_batch_lookup_dev(
-            0, ctypes.byref(t), _ptr(self.keys), c.cap,
+            0, ctypes.byref(t), ptr(self.keys), c.cap,
             None if self.nkeys is None else self.nkeys.data_ptr(), c.mode, c.missing, c.limit,
             self.outs["vals"].data_ptr() if "vals" in self.outs else None,
             self.outs["pos"].data_ptr() if "pos" in self.outs else None, stream.cuda_stream)
@@ -88,12 +75,12 @@ class DevAcc:
         self.c, self.fill = c, fill
         s = 8 if skew else 0
         self.table = None if c.table is None else DevTable(c.table, s)
-        self.keys, self.adds = _up(c.keys, s), _up(c.adds, s)
-        self.nkeys = None if c.nkeys is None else _up(np.array([c.nkeys], dtype=U64))
-        self.outs = {"keys": _up(np.full(c.out_cap + GUARD, fill["keys"], dtype=U64), s),
-                     "vals": _up(np.full(c.out_cap + GUARD, fill["keys"], dtype=U64), s),
-                     "n": _up(np.full(1 + GUARD, fill["n"], dtype=U64), s),
-                     "info": _up(np.full(3 + GUARD, fill["info"], dtype=U64), s)}
+        self.keys, self.adds = up(c.keys, s), up(c.adds, s)
+        self.nkeys = None if c.nkeys is None else up(np.array([c.nkeys], dtype=U64))
+        self.outs = {"keys": up(np.full(c.out_cap + GUARD, fill["keys"], dtype=U64), s),
+                     "vals": up(np.full(c.out_cap + GUARD, fill["keys"], dtype=U64), s),
+                     "n": up(np.full(1 + GUARD, fill["n"], dtype=U64), s),
+                     "info": up(np.full(3 + GUARD, fill["info"], dtype=U64), s)}
 
     def enqueue(self, gpu, stream):
         c = self.c
@@ -103,7 +90,7 @@ class DevAcc:
                             self.outs["vals"].data_ptr() if cap else None, cap,
                             self.outs["n"].data_ptr())
         return gpu.lib().ebpf_batch_accumulate_dev(
-            0, None if tin is None else ctypes.byref(tin), _ptr(self.keys), _ptr(self.adds), c.cap,
+            0, None if tin is None else ctypes.byref(tin), ptr(self.keys), ptr(self.adds), c.cap,
             None if self.nkeys is None else self.nkeys.data_ptr(), c.op, c.lo, c.hi,
             ctypes.byref(tout), self.outs["info"].data_ptr(), stream.cuda_stream)
 
@@ -117,13 +104,6 @@ class DevAcc:
         for k in w:
             np.testing.assert_array_equal(got[k], w[k], err_msg="%s: %s" % (msg, k))
         return got
-
-
-def run(gpu, devs):
-    import torch
-    for d in devs:
-        assert d.enqueue(gpu, torch.cuda.current_stream()) == 0
-    torch.cuda.synchronize()
 
 
 def adds_for(r, seed=0):
@@ -380,7 +360,7 @@ def test_quota_across_two_batches_on_one_stream(gpu, env):
     try:
         for b, (flow, lens, offsets, data) in enumerate(batches):
             n = len(flow)
-            d_data, d_offs = _up(data), _up(offsets)
+            d_data, d_offs = up(data), up(offsets)
             ret, flt = z(n, torch.int64, -1), z(n, torch.uint8)
             index, gkeys, gstarts = z(n, torch.int32, -1), z(cap, torch.int64), z(cap + 1, torch.int64)
             info, kd, tinfo = z(2, torch.int64), z(2, torch.int64), z(3, torch.int64)

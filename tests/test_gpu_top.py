@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from generic_ebpf_amd import native as _native
+from gpu_buffers import ptr, run, up
 from test_top import (ALL, FIELDS, FILL, GUARD, LARGEST, MAXU, PATTERNS, SEGMENTS, SMALLEST, TYPES,
                       U64, Top, host_top, values)
 
@@ -31,38 +32,24 @@ OTHER = {"keys": 0x0123456789abcdef, "vals": 0x0123456789abcdef, "pos": 0x012345
          "info": 0x0123456789abcdef}
 
 
-def _up(a, skew=0):
-    """a on the device; skew: that many bytes past a 256-byte boundary"""
-    import torch
-    a = np.ascontiguousarray(a).view(np.uint8)
-    buf = torch.zeros(len(a) + 256, dtype=torch.uint8, device="cuda:0")
-    assert buf.data_ptr() % 256 == 0
-    buf[skew:skew + len(a)] = torch.from_numpy(a)
-    return buf[skew:skew + len(a)]
-
-
-def _ptr(t):
-    return t.data_ptr() if t.numel() else None
-
-
 class DevTop:
     """a Top's arrays and outputs on the device"""
 
     def __init__(self, c, fill=FILL, skew=False):
         self.c, self.fill = c, fill
         s = 8 if skew else 0
-        self.keys = None if c.keys is None else _up(c.keys, s)
-        self.vals = _up(c.vals, s)
-        self.n = None if c.n is None else _up(np.array([c.n], dtype=U64), s)
-        self.outs = {w: _up(np.full(c.k + GUARD, fill[w], dtype=TYPES[w]),
+        self.keys = None if c.keys is None else up(c.keys, s)
+        self.vals = up(c.vals, s)
+        self.n = None if c.n is None else up(np.array([c.n], dtype=U64), s)
+        self.outs = {w: up(np.full(c.k + GUARD, fill[w], dtype=TYPES[w]),
                             (4 if w == "pos" else 8) if skew else 0) for w in c.want}
-        self.outs["info"] = _up(np.full(4 + GUARD, fill["info"], dtype=U64), s)
+        self.outs["info"] = up(np.full(4 + GUARD, fill["info"], dtype=U64), s)
 
     def enqueue(self, gpu, stream):
         c = self.c
         tops = gpu.BatchTops(*[self.outs[w].data_ptr() if w in c.want else None for w in ALL])
         return gpu.lib().ebpf_batch_top_dev(
-            0, None if self.keys is None else self.keys.data_ptr() or 16, _ptr(self.vals), c.cap,
+            0, None if self.keys is None else self.keys.data_ptr() or 16, ptr(self.vals), c.cap,
             None if self.n is None else self.n.data_ptr(), c.flags, c.field[0], c.field[1], c.k,
             ctypes.byref(tops), self.outs["info"].data_ptr(), stream.cuda_stream)
 
@@ -74,13 +61,6 @@ class DevTop:
         for k in w:
             np.testing.assert_array_equal(got[k], w[k], err_msg="%s: %s" % (msg, k))
         return got
-
-
-def run(gpu, devs):
-    import torch
-    for d in devs:
-        assert d.enqueue(gpu, torch.cuda.current_stream()) == 0
-    torch.cuda.synchronize()
 
 
 def check_all(gpu, devs):
@@ -307,7 +287,7 @@ def test_heaviest_flows_of_two_batches_on_one_stream(gpu, env):
     try:
         for b, (flow, lens, offsets, data) in enumerate(batches):
             n = len(flow)
-            d_data, d_offs = _up(data), _up(offsets)
+            d_data, d_offs = up(data), up(offsets)
             ret, flt = z(n, torch.int64, -1), z(n, torch.uint8)
             index, gkeys, gstarts = z(n, torch.int32, -1), z(cap, torch.int64), z(cap + 1, torch.int64)
             info, tinfo = z(2, torch.int64), z(3, torch.int64)
